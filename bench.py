@@ -15,6 +15,13 @@ reference run, ``total_steps=100000`` at ``grid_chain_sec11.py:342``; 10 timed s
 1e6 steps per chain of BASELINE config C2).  Inputs are resident in HBM before the
 timed region; the timed region is bracketed by barrier + device synchronisation.
 
+A plain run does what the headline figure needs and no more: set up, ``--warmup`` launches,
+``--steps`` timed launches, the result line (``ms_per_step`` = the timed region over ``--steps``).
+``--full`` adds the side lines, each after the timed region and under its own option: the CPU
+baselines, the full-diagnostics leg, the reference's two sweeps, the node-stream comparison of a
+band run.  ``--dump-outputs DIR`` writes the chain states and per-chain statistics the last timed
+launch left as ``DIR/<name>.npy`` (``dump_outputs``), for comparing two builds output for output.
+
 N > 1: one process per GPU, chains sharded by global id with no data-path collective (weak
 scaling); one RCCL all-reduce of the statistics at the end.  Under ``torch.distributed.run``
 the ranks come from the environment and ``--gpus`` must equal ``WORLD_SIZE``; run directly
@@ -298,6 +305,35 @@ def sweep_leg(replicas: int, device: int) -> dict:
                     "and population bounds), full diagnostics + event log + corrected tallies, every "
                     "configuration's files written by ChainResult.write_outputs (the reference runs the 174 "
                     "configurations one after another on one CPU thread)"}
+
+
+DUMP_BUDGET = 64 * 1000 * 1000  # bytes, all the files of one --dump-outputs together
+
+
+def dump_outputs(dirname: str, run, stats: dict, rank: int = 0, world: int = 1) -> dict:
+    """``--dump-outputs DIR``: what the timed path left after its last launch, as a caller reads it
+    back -- ``state.npy`` (float32, chains x nodes: ``FlipRun.state()``, the district index of every
+    node) and one ``stats_<field>.npy`` (float64, one entry per chain: ``FlipRun.stats()``; counters
+    beyond 2^53 round).  The inputs are fixed by the arguments (start plans, bases, Philox seed), so
+    two builds run with the same arguments write comparable files.  A state larger than the budget
+    is written for a fixed, seeded sample of chains; ``state_chains.npy`` holds their local ids.
+    N > 1: every rank writes its shard with a ``_rank<r>`` suffix."""
+    os.makedirs(dirname, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    state = run.state()
+    n_chains, n = state.shape
+    arrays = {f"stats_{k}": np.asarray(v, dtype=np.float64) for k, v in stats.items()}
+    room = DUMP_BUDGET - sum(a.nbytes + 256 for a in arrays.values()) - 8 * n_chains - 512
+    rows = max(1, min(n_chains, room // (4 * n)))
+    chains = np.arange(n_chains)
+    if rows < n_chains:
+        chains = np.sort(np.random.default_rng(SEED).choice(n_chains, size=rows, replace=False))
+    arrays["state"] = state[chains].astype(np.float32)
+    arrays["state_chains"] = chains.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, f"{name}{sfx}.npy"), a)
+    return {"dir": dirname, "files": len(arrays), "bytes": int(sum(a.nbytes for a in arrays.values())),
+            "state_chains": int(rows), "state_sampled": bool(rows < n_chains)}
 
 
 def _free_port() -> int:
@@ -613,8 +649,10 @@ def recom_leg(args) -> dict:
                         "note": "per spanning tree: adjacency 4 B x 2E + edge weight 4 B x E + parent / subtree "
                                 "population 8 B x n + assignment 1 B x n, against the LDS b32 aggregate "
                                 "(MI355X_MICROARCH.md §LDS: 128 B/clk/CU x 256 CUs x 2.4 GHz)"}}
+    if args.dump_outputs:
+        out["outputs"] = dump_outputs(args.dump_outputs, run, s1)
     run.close()
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         cores, share = host_cpu_share()
         from concurrent.futures import ProcessPoolExecutor
         with ProcessPoolExecutor(max_workers=cores) as ex:
@@ -651,6 +689,13 @@ def main():
     ap.add_argument("--chain-steps", type=int, default=100000)
     ap.add_argument("--chains", type=int, default=0, help="chains per GPU (0: the workload's)")
     ap.add_argument("--workload", default="c2", choices=["c2", "c3", "c4", "c5", "recom"])
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side line after the timed steps: the CPU baselines, the full-diagnostics "
+                         "leg, the reference's two sweeps, the node-stream comparison of a band run (each still "
+                         "switched by its own option below); off: set up, warm up, time --steps launches, print")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed launch left -- the chain states and the "
+                         "per-chain statistics a caller reads back -- as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--sweep-replicas", type=int, default=1,
@@ -747,6 +792,8 @@ def main():
     launch_ms = run.timings()
     s1 = run.stats()
     kname = run.kernel_name()
+    # outside the timed region, before any side line closes the run: the last launch's outputs
+    dumped = dump_outputs(args.dump_outputs, run, s1, rank, world) if args.dump_outputs else None
 
     elapsed = t1 - t0
     props = float((s1["proposals"] - s0["proposals"]).sum())
@@ -775,7 +822,7 @@ def main():
         raise SystemExit(f"bench.py: ranks share a device: {devices['per_rank']}")
 
     node_out = None
-    if stream == "band" and args.node_stream_steps > 0:
+    if args.full and stream == "band" and args.node_stream_steps > 0:
         # beside it (outside the timed region): the same workload on the node stream, whose draws
         # range over all n nodes (the round-2 kernel's stream)
         run.close()
@@ -804,7 +851,7 @@ def main():
         rn.close()
 
     full_out = None
-    if args.full_diag_steps > 0:
+    if args.full and args.full_diag_steps > 0:
         # side line, outside the timed region above and on every rank: the same workload with
         # every per-yield tally of the reference's driver loop on (grid_chain_sec11.py:366-402:
         # cut / |B| histograms, per-edge cut_times, per-node num_flips / part_sum /
@@ -1065,11 +1112,13 @@ def main():
     }
     if full_out is not None:
         out["full_diagnostics"] = full_out
-    if world == 1 and args.workload == "c2" and args.sweep_replicas > 0:
+    if dumped is not None:
+        out["outputs"] = dumped
+    if args.full and world == 1 and args.workload == "c2" and args.sweep_replicas > 0:
         out["reference_sweeps"] = sweep_leg(args.sweep_replicas, local_rank)
     if node_out is not None:
         out["node_stream"] = node_out
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         # rank 0 only (the other ranks have left), after every collective and outside the timed
         # region, so an N-GPU line carries its CPU baseline too: one process per CPU this job can
         # use -- every host core, unless the affinity set or a cgroup quota grants fewer (then the
