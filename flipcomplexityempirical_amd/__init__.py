@@ -11,6 +11,7 @@ Layers:
   engine       FlipGraph / FlipRun over the C-ABI of libflipchain.so
   chain        gerrychain-shaped drop-in API (Partition, MarkovChain, Validator, ...)
   distributed  chain sharding over GPUs + RCCL reduction of statistics
+  tempering    replica exchange between the chains of one run (ladders, per-rung statistics)
 """
 from .graphs import GraphSpec  # noqa: F401
 

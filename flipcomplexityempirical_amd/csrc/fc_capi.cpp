@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "fc_internal.h"
+#include "fc_ladder.h"
 #include "fc_philox.h"
 
 struct fc_graph {
@@ -104,6 +105,21 @@ struct fc_run {
         float prio_th[3];
     } tune{};
     size_t ev_head = 0;          // launch_events: oldest recorded pair (ring of kMaxLaunchEvents)
+    // replica exchange (fc_run_set_ladders; fc_ladder.h, fc_exchange.hip).  Slots are flat: ladder
+    // l's rung r is slot lad_off[l] + r
+    std::vector<double> bases0;        // [n_chains] the base each chain was created with
+    std::vector<int64_t> pop_bounds;   // [2 * n_chains]
+    std::vector<int32_t> lad_off, lad_members, lad_slot_ladder;  // [L + 1], [M], [M]
+    uint32_t lad_hash = 0;             // hash of the layout, the checkpoint header's word (0: no ladders)
+    uint64_t ex_round = 0;             // exchange rounds so far
+    int32_t lad_n_items[3] = {0, 0, 0};  // work items of parity 0 / 1 and of the attribute-only pass
+    fc::LadderItem *d_lad_items[3] = {nullptr, nullptr, nullptr};
+    fc::LadderSlot *d_lad_slots = nullptr;
+    fc::LadderPair *d_lad_pairs = nullptr;
+    int32_t *d_slot_of = nullptr, *d_chain_at = nullptr;
+    int64_t *d_lad_snap = nullptr;     // [n_chains * kRungFields]
+    fc_rung_stats *d_rung = nullptr;   // [M]
+    int64_t *d_snap_cut = nullptr, *d_snap_nb = nullptr, *d_rung_cut = nullptr, *d_rung_nb = nullptr;
 };
 
 namespace {
@@ -137,6 +153,8 @@ void free_run(fc_run *r) {
     void *bufs[] = {r->d_graph, r->d_ring_eid, r->d_assign, r->d_fcnt, r->d_sc, r->d_thresh, r->d_log1mp,
                     r->d_labels, r->d_cut_hist, r->d_nb_hist, r->d_edge_acc,
                     r->d_num_flips, r->d_part_sum, r->d_last_flipped, r->d_flip_count, r->d_occ_acc, r->d_last_accept, r->d_trace, r->d_tape, r->d_popk, r->d_nfh, r->d_sbits, r->d_mcnt, r->d_ngk, r->d_events, r->d_prof, r->d_eta, r->d_deal, r->d_order, r->d_ctime, r->d_ser_a0, r->d_eu, r->d_ev, r->d_nbe, r->d_eslot, r->d_recom_thresh, r->d_tl, r->d_tl_len, r->d_tl_t0,
+                    r->d_lad_items[0], r->d_lad_items[1], r->d_lad_items[2], r->d_lad_slots, r->d_lad_pairs, r->d_slot_of,
+                    r->d_chain_at, r->d_lad_snap, r->d_rung, r->d_snap_cut, r->d_snap_nb, r->d_rung_cut, r->d_rung_nb,
                     r->d_fs_out, r->d_fs_cnt, r->d_fc_fuv, r->d_fc_tidx, r->d_fc_tog, r->d_fc_mid, r->d_fc_len,
                     r->d_fc_t0, r->d_fc_cnt, r->d_fc_off, r->d_fc_t, r->d_fc_sa, r->d_fc_wcnt, r->d_st_t, r->d_st_sa};
     for (void *b : bufs)
@@ -422,6 +440,9 @@ int fc_run_create(const fc_graph *gr, const fc_params *p, int32_t n_chains, cons
     r->p.con_valid = con_valid;
     r->variant = variant;
     r->n_chains = n_chains;
+    r->pop_bounds = pop_bounds;
+    r->bases0.resize(n_chains);
+    for (int32_t c = 0; c < n_chains; ++c) r->bases0[c] = bases ? bases[c] : p->base;
     r->npad = (n + 15) & ~15;
     r->words = (n + 63) / 64;
     if (g.max_degree > 16)  // dev::wave_bfs labels each old neighbour with a 4-bit id
@@ -1212,13 +1233,31 @@ static std::vector<std::pair<void *, size_t>> ckpt_sections(fc_run *r) {
         v.emplace_back(r->d_events, C * (size_t)r->ev_cap * sizeof(fc_event));
         v.emplace_back(r->d_ser_a0, C * r->npad);
     }
+    if (r->lad_hash) {  // replica exchange: rung map, snapshots, per-slot sums and swap counters, histograms
+        const size_t M = r->lad_members.size();
+        v.emplace_back(r->d_slot_of, C * 4);
+        v.emplace_back(r->d_chain_at, M * 4);
+        v.emplace_back(r->d_lad_snap, C * fc::kRungFields * 8);
+        v.emplace_back(r->d_rung, M * sizeof(fc_rung_stats));
+        if (r->d_snap_cut) {
+            const size_t cw2 = (E + 2) & ~(size_t)1, nw2 = ((size_t)r->nb_w + 1) & ~(size_t)1;
+            v.emplace_back(r->d_snap_cut, C * cw2 * 8);
+            v.emplace_back(r->d_snap_nb, C * nw2 * 8);
+            v.emplace_back(r->d_rung_cut, M * cw2 * 8);
+            v.emplace_back(r->d_rung_nb, M * nw2 * 8);
+        }
+    }
     return v;
 }
+
+// bytes after the device sections: the exchange round counter (runs with ladders only)
+size_t ckpt_tail_bytes(const fc_run *r) { return r->lad_hash ? 8 : 0; }
 
 CkptHeader ckpt_header(const fc_run *r, int64_t payload) {
     CkptHeader h{};
     std::memcpy(h.magic, "FCCKPT03", 8);
     h.stream_version = kStreamVersion;
+    h.reserved = r->lad_hash;  // hash of the ladder layout (fc_run_set_ladders), 0: no ladders
     h.n_chains = r->n_chains;
     h.n = r->g.n;
     h.n_edges = r->g.n_edges;
@@ -1243,6 +1282,7 @@ int fc_run_checkpoint(fc_run *r, void *buf, int64_t cap, int64_t *len) {
     const auto secs = ckpt_sections(r);
     int64_t payload = 0;
     for (const auto &sc : secs) payload += (int64_t)sc.second;
+    payload += (int64_t)ckpt_tail_bytes(r);
     const int64_t total = (int64_t)sizeof(CkptHeader) + payload;
     *len = total;
     if (!buf) return FC_OK;
@@ -1256,6 +1296,7 @@ int fc_run_checkpoint(fc_run *r, void *buf, int64_t cap, int64_t *len) {
         if (sc.second) HIP_TRY(hipMemcpy(out + off, sc.first, sc.second, hipMemcpyDeviceToHost));
         off += sc.second;
     }
+    if (ckpt_tail_bytes(r)) std::memcpy(out + off, &r->ex_round, 8);
     return FC_OK;
 }
 
@@ -1267,6 +1308,7 @@ int fc_run_restore(fc_run *r, const void *buf, int64_t len) {
     const auto secs = ckpt_sections(r);
     int64_t payload = 0;
     for (const auto &sc : secs) payload += (int64_t)sc.second;
+    payload += (int64_t)ckpt_tail_bytes(r);
     const CkptHeader want = ckpt_header(r, payload);
     if (std::memcmp(h.magic, "FCCKPT02", 8) == 0)
         return fail(FC_ERR_ARG, "fc_run_restore: the checkpoint was written under an earlier random stream (FCCKPT02: one "
@@ -1275,6 +1317,8 @@ int fc_run_restore(fc_run *r, const void *buf, int64_t len) {
     if (h.stream_version != kStreamVersion)
         return fail(FC_ERR_ARG, "fc_run_restore: the checkpoint's random-stream version (" + std::to_string(h.stream_version) +
                                     ") differs from this build's (" + std::to_string(kStreamVersion) + ")");
+    if (h.reserved != want.reserved)
+        return fail(FC_ERR_ARG, "fc_run_restore: the checkpoint's ladders (fc_run_set_ladders) differ from this run's");
     if (h.n_chains != want.n_chains || h.n != want.n || h.n_edges != want.n_edges || h.k != want.k ||
         h.ring_max != want.ring_max || h.proposal != want.proposal || h.npad != want.npad || h.dgraph != want.dgraph ||
         h.diag_mask != want.diag_mask || h.ev_cap != want.ev_cap || h.payload != payload)
@@ -1289,6 +1333,25 @@ int fc_run_restore(fc_run *r, const void *buf, int64_t len) {
     if (int rc = fc_run_sync(r)) return rc;
     const unsigned char *in = (const unsigned char *)buf;
     size_t off = sizeof h;
+    if (r->lad_hash) {  // the rung map must be a permutation inside every ladder (the kernel indexes by it)
+        size_t o = off;
+        for (const auto &sc : secs) {
+            if (sc.first == (void *)r->d_slot_of) break;
+            o += sc.second;
+        }
+        const size_t C = (size_t)r->n_chains, M = r->lad_members.size();
+        std::vector<int32_t> so(C), ca(M);
+        std::memcpy(so.data(), in + o, C * 4);
+        std::memcpy(ca.data(), in + o + C * 4, M * 4);
+        bool ok = true;
+        for (size_t c = 0; c < C && ok; ++c) ok = so[c] >= -1 && so[c] < (int32_t)M && (so[c] < 0 || ca[so[c]] == (int32_t)c);
+        for (size_t m = 0; m < M && ok; ++m)
+            ok = ca[m] >= 0 && ca[m] < (int32_t)C && so[ca[m]] == (int32_t)m;
+        std::vector<int32_t> home(C, -1);  // a chain stays in the ladder it was listed in
+        for (size_t m = 0; m < M; ++m) home[r->lad_members[m]] = r->lad_slot_ladder[m];
+        for (size_t m = 0; m < M && ok; ++m) ok = home[ca[m]] == r->lad_slot_ladder[m];
+        if (!ok) return fail(FC_ERR_ARG, "fc_run_restore: the checkpoint's rung map is not a permutation of this run's ladders");
+    }
     for (size_t i = 0; i < secs.size(); ++i) {
         const auto &sc = secs[i];
         if (i == 1) {  // ChainScalars: traces are outputs and restart empty
@@ -1301,7 +1364,220 @@ int fc_run_restore(fc_run *r, const void *buf, int64_t len) {
         }
         off += sc.second;
     }
+    if (ckpt_tail_bytes(r)) std::memcpy(&r->ex_round, in + off, 8);
     r->deal_timed = false;  // the restored chains' pace is not the last launch's
+    return FC_OK;
+}
+
+// ---- replica exchange (fc_ladder.h, fc_exchange.hip; DESIGN.md "Replica exchange") -----------
+
+int fc_ladder_swap_threshold(double b_lo_rung, double b_hi_rung, int32_t d, uint64_t *t) {
+    if (!t) return fail(FC_ERR_ARG, "fc_ladder_swap_threshold: null output");
+    if (!(b_lo_rung > 0.0) || !(b_hi_rung > 0.0) || !std::isfinite(b_lo_rung) || !std::isfinite(b_hi_rung))
+        return fail(FC_ERR_ARG, "fc_ladder_swap_threshold: bases must be positive and finite");
+    if (d <= -(1 << fc::kLadderBits) || d >= (1 << fc::kLadderBits))
+        return fail(FC_ERR_ARG, "fc_ladder_swap_threshold: |d| must be below 2^17");
+    const fc::LadderPair tab = fc::ladder_pair(b_lo_rung, b_hi_rung);
+    *t = fc::ladder_threshold(tab, d);
+    return FC_OK;
+}
+
+int fc_run_set_ladders(fc_run *r, int32_t n_ladders, const int32_t *ladder_off, const int32_t *members,
+                       uint32_t flags) {
+    if (!r || !ladder_off || !members || n_ladders <= 0)
+        return fail(FC_ERR_ARG, "fc_run_set_ladders: null argument or n_ladders <= 0");
+    if (r->p.proposal == FC_PROPOSE_RECOM)
+        return fail(FC_ERR_UNSUPPORTED, "fc_run_set_ladders: replica exchange is for flip proposals (not ReCom)");
+    if (r->p.accept != FC_ACCEPT_CUT)
+        return fail(FC_ERR_UNSUPPORTED, "fc_run_set_ladders: replica exchange needs FC_ACCEPT_CUT (the swap rule is "
+                                        "the ratio of cut_accept's stationary weights)");
+    if (r->g.n_edges >= (1 << fc::kLadderBits))
+        return fail(FC_ERR_UNSUPPORTED, "fc_run_set_ladders: the swap table covers |cut| differences below 2^17 edges");
+    if (r->lad_hash) return fail(FC_ERR_ARG, "fc_run_set_ladders: ladders are already set (callable once)");
+    if (flags & ~FC_LADDER_HIST) return fail(FC_ERR_ARG, "fc_run_set_ladders: unknown flags");
+    if ((flags & FC_LADDER_HIST) && !r->d_cut_hist)
+        return fail(FC_ERR_ARG, "fc_run_set_ladders: FC_LADDER_HIST needs a run with FC_DIAG_HIST");
+    const int32_t C = r->n_chains;
+    if (ladder_off[0] != 0) return fail(FC_ERR_ARG, "fc_run_set_ladders: ladder_off[0] must be 0");
+    for (int32_t l = 0; l < n_ladders; ++l)
+        if (ladder_off[l + 1] <= ladder_off[l] || ladder_off[l + 1] > C)
+            return fail(FC_ERR_ARG, "fc_run_set_ladders: ladder " + std::to_string(l) + " is empty or ladder_off is not "
+                                    "increasing within n_chains (a chain belongs to at most one ladder)");
+    const int32_t M = ladder_off[n_ladders];
+    std::vector<int32_t> slot_of((size_t)C, -1), slot_ladder((size_t)M);
+    std::vector<fc::LadderSlot> slots((size_t)M);
+    std::vector<fc::LadderPair> pairs((size_t)M);
+    std::vector<fc::LadderItem> items[3];
+    for (int32_t l = 0; l < n_ladders; ++l) {
+        const int32_t lo = ladder_off[l], hi = ladder_off[l + 1];
+        for (int32_t s = lo; s < hi; ++s) {
+            const int32_t c = members[s];
+            if (c < 0 || c >= C)
+                return fail(FC_ERR_ARG, "fc_run_set_ladders: chain index " + std::to_string(c) + " out of range");
+            if (slot_of[c] >= 0)
+                return fail(FC_ERR_ARG, "fc_run_set_ladders: chain " + std::to_string(c) + " is listed twice");
+            if (r->pop_bounds[2 * (size_t)c] != r->pop_bounds[2 * (size_t)members[lo]] ||
+                r->pop_bounds[2 * (size_t)c + 1] != r->pop_bounds[2 * (size_t)members[lo] + 1])
+                return fail(FC_ERR_ARG, "fc_run_set_ladders: the chains of ladder " + std::to_string(l) +
+                                            " have different population bounds (bounds are never swapped)");
+            const double b = r->bases0[c];
+            if (!(b > 0.0) || !std::isfinite(b))
+                return fail(FC_ERR_ARG, "fc_run_set_ladders: chain " + std::to_string(c) + " has a non-positive base");
+            slot_of[c] = s;
+            slot_ladder[s] = l;
+            slots[s].rung = s - lo;
+            slots[s].gid = r->p.chain_id_offset + (uint32_t)members[lo];
+        }
+        for (int32_t s = lo; s < hi; ++s) {
+            pairs[s] = s + 1 < hi ? fc::ladder_pair(r->bases0[members[s]], r->bases0[members[s + 1]]) : fc::LadderPair{};
+            items[2].push_back({s, 0});
+        }
+        for (int par = 0; par < 2; ++par)  // pairs (rung, rung + 1) with rung = par (mod 2); the rest unpaired
+            for (int32_t s = lo; s < hi;) {
+                const bool pr = ((s - lo) & 1) == par && s + 1 < hi;
+                items[par].push_back({s, pr ? 1 : 0});
+                s += pr ? 2 : 1;
+            }
+    }
+    HIP_TRY(hipSetDevice(r->p.device));
+    int rc;
+    for (int i = 0; i < 3; ++i) {
+        if ((rc = dalloc(&r->d_lad_items[i], items[i].size()))) return rc;
+        HIP_TRY(hipMemcpy(r->d_lad_items[i], items[i].data(), items[i].size() * sizeof(fc::LadderItem), hipMemcpyHostToDevice));
+        r->lad_n_items[i] = (int32_t)items[i].size();
+    }
+    if ((rc = dalloc(&r->d_lad_slots, (size_t)M))) return rc;
+    if ((rc = dalloc(&r->d_lad_pairs, (size_t)M))) return rc;
+    if ((rc = dalloc(&r->d_slot_of, (size_t)C))) return rc;
+    if ((rc = dalloc(&r->d_chain_at, (size_t)M))) return rc;
+    if ((rc = dalloc(&r->d_lad_snap, (size_t)C * fc::kRungFields))) return rc;
+    if ((rc = dalloc(&r->d_rung, (size_t)M))) return rc;
+    HIP_TRY(hipMemcpy(r->d_lad_slots, slots.data(), (size_t)M * sizeof(slots[0]), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(r->d_lad_pairs, pairs.data(), (size_t)M * sizeof(pairs[0]), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(r->d_slot_of, slot_of.data(), (size_t)C * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(r->d_chain_at, members, (size_t)M * 4, hipMemcpyHostToDevice));
+    // snapshots start at zero: what a chain accumulated so far (the initial yield included) goes
+    // to its initial rung at the first attribution
+    HIP_TRY(hipMemset(r->d_lad_snap, 0, (size_t)C * fc::kRungFields * 8));
+    HIP_TRY(hipMemset(r->d_rung, 0, (size_t)M * sizeof(fc_rung_stats)));
+    if (flags & FC_LADDER_HIST) {
+        const size_t cw2 = ((size_t)r->g.n_edges + 2) & ~(size_t)1, nw2 = ((size_t)r->nb_w + 1) & ~(size_t)1;
+        struct { int64_t **p; size_t count; } bufs[] = {{&r->d_snap_cut, (size_t)C * cw2}, {&r->d_snap_nb, (size_t)C * nw2},
+                                                        {&r->d_rung_cut, (size_t)M * cw2}, {&r->d_rung_nb, (size_t)M * nw2}};
+        bool ok = true;
+        for (auto &b : bufs) ok = ok && hipMalloc((void **)b.p, b.count * 8) == hipSuccess;
+        if (!ok) {
+            (void)hipGetLastError();
+            for (auto &b : bufs) { if (*b.p) (void)hipFree(*b.p); *b.p = nullptr; }
+            // nothing of the ladders stays behind: the call may be repeated without the flag
+            void **small[] = {(void **)&r->d_lad_items[0], (void **)&r->d_lad_items[1], (void **)&r->d_lad_items[2],
+                              (void **)&r->d_lad_slots, (void **)&r->d_lad_pairs, (void **)&r->d_slot_of,
+                              (void **)&r->d_chain_at, (void **)&r->d_lad_snap, (void **)&r->d_rung};
+            for (void **q : small) { if (*q) (void)hipFree(*q); *q = nullptr; }
+            return fail(FC_ERR_NOMEM, "fc_run_set_ladders: the FC_LADDER_HIST buffers do not fit in device memory");
+        }
+        for (auto &b : bufs) HIP_TRY(hipMemset(*b.p, 0, b.count * 8));
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    r->lad_off.assign(ladder_off, ladder_off + n_ladders + 1);
+    r->lad_members.assign(members, members + M);
+    r->lad_slot_ladder = slot_ladder;
+    uint64_t h = 0xcbf29ce484222325ull;
+    h = fnv1a(h, r->lad_off.data(), r->lad_off.size() * 4);
+    h = fnv1a(h, r->lad_members.data(), r->lad_members.size() * 4);
+    h = fnv1a(h, &flags, 4);
+    r->lad_hash = (uint32_t)(h ^ (h >> 32));
+    if (!r->lad_hash) r->lad_hash = 1;
+    return FC_OK;
+}
+
+static int enqueue_exchange(fc_run *r, int which, bool do_swap, hipStream_t s) {
+    fc::ExchangeParams q{};
+    q.items = r->d_lad_items[which];
+    q.n_items = r->lad_n_items[which];
+    q.do_swap = do_swap ? 1 : 0;
+    q.round = (uint32_t)r->ex_round;
+    q.seed_lo = (uint32_t)r->p.seed;
+    q.seed_hi = (uint32_t)(r->p.seed >> 32);
+    q.slots = r->d_lad_slots;
+    q.pairs = r->d_lad_pairs;
+    q.slot_of = r->d_slot_of;
+    q.chain_at = r->d_chain_at;
+    q.sc = r->d_sc;
+    q.thresh = r->d_thresh;
+    q.tw = 2 * r->g.ring_max + 1;
+    q.snap = r->d_lad_snap;
+    q.rung = r->d_rung;
+    if (r->d_snap_cut) {
+        q.cut_hist = r->d_cut_hist;
+        q.nb_hist = r->d_nb_hist;
+        q.snap_cut = r->d_snap_cut;
+        q.snap_nb = r->d_snap_nb;
+        q.rung_cut = r->d_rung_cut;
+        q.rung_nb = r->d_rung_nb;
+        q.cut_w = r->g.n_edges + 1;
+        q.nb_w = r->nb_w;
+        q.cut_w2 = (q.cut_w + 1) & ~1;
+        q.nb_w2 = (q.nb_w + 1) & ~1;
+    }
+    const int e = fc::launch_exchange(q, s);
+    if (e != 0) return fail(FC_ERR_HIP, std::string("exchange kernel launch: ") + hipGetErrorString((hipError_t)e));
+    return FC_OK;
+}
+
+int fc_run_exchange(fc_run *r, int32_t parity, void *hip_stream) {
+    if (!r) return fail(FC_ERR_ARG, "fc_run_exchange: null run");
+    if (!r->lad_hash) return fail(FC_ERR_ARG, "fc_run_exchange: no ladders (fc_run_set_ladders)");
+    if (parity < -1 || parity > 1) return fail(FC_ERR_ARG, "fc_run_exchange: parity must be 0, 1 or -1 (round & 1)");
+    HIP_TRY(hipSetDevice(r->p.device));
+    const int par = parity < 0 ? (int)(r->ex_round & 1) : parity;
+    if (int rc = enqueue_exchange(r, par, true, hip_stream ? (hipStream_t)hip_stream : r->stream)) return rc;
+    ++r->ex_round;
+    return FC_OK;
+}
+
+int fc_run_read_rungs(fc_run *r, int32_t *rung_of, int32_t *chain_at) {
+    if (!r) return fail(FC_ERR_ARG, "fc_run_read_rungs: null run");
+    if (!r->lad_hash) return fail(FC_ERR_ARG, "fc_run_read_rungs: no ladders (fc_run_set_ladders)");
+    if (int rc = fc_run_sync(r)) return rc;
+    if (rung_of) {
+        HIP_TRY(hipMemcpy(rung_of, r->d_slot_of, (size_t)r->n_chains * 4, hipMemcpyDeviceToHost));
+        for (int32_t c = 0; c < r->n_chains; ++c)
+            if (rung_of[c] >= 0) rung_of[c] -= r->lad_off[r->lad_slot_ladder[rung_of[c]]];
+    }
+    if (chain_at) HIP_TRY(hipMemcpy(chain_at, r->d_chain_at, r->lad_members.size() * 4, hipMemcpyDeviceToHost));
+    return FC_OK;
+}
+
+int fc_run_read_bases(fc_run *r, double *bases) {
+    if (!r || !bases) return fail(FC_ERR_ARG, "fc_run_read_bases: null argument");
+    std::copy(r->bases0.begin(), r->bases0.end(), bases);
+    if (!r->lad_hash) return FC_OK;
+    if (int rc = fc_run_sync(r)) return rc;
+    std::vector<int32_t> so((size_t)r->n_chains);
+    HIP_TRY(hipMemcpy(so.data(), r->d_slot_of, so.size() * 4, hipMemcpyDeviceToHost));
+    // a slot keeps the base of the chain listed there: temperatures move, slots do not
+    for (int32_t c = 0; c < r->n_chains; ++c)
+        if (so[c] >= 0) bases[c] = r->bases0[r->lad_members[so[c]]];
+    return FC_OK;
+}
+
+int fc_run_read_rung_stats(fc_run *r, fc_rung_stats *out, int64_t *cut_hist, int64_t *nb_hist) {
+    if (!r || !out) return fail(FC_ERR_ARG, "fc_run_read_rung_stats: null argument");
+    if (!r->lad_hash) return fail(FC_ERR_ARG, "fc_run_read_rung_stats: no ladders (fc_run_set_ladders)");
+    if ((cut_hist || nb_hist) && !r->d_snap_cut)
+        return fail(FC_ERR_ARG, "fc_run_read_rung_stats: the per-rung histograms need FC_LADDER_HIST");
+    HIP_TRY(hipSetDevice(r->p.device));
+    HIP_TRY(hipDeviceSynchronize());  // launches on a caller's stream included
+    if (int rc = enqueue_exchange(r, 2, false, r->stream)) return rc;
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    const size_t M = r->lad_members.size();
+    HIP_TRY(hipMemcpy(out, r->d_rung, M * sizeof(fc_rung_stats), hipMemcpyDeviceToHost));
+    const size_t cw = (size_t)r->g.n_edges + 1, nw = (size_t)r->nb_w;
+    if (cut_hist)
+        HIP_TRY(hipMemcpy2D(cut_hist, cw * 8, r->d_rung_cut, ((cw + 1) & ~(size_t)1) * 8, cw * 8, M, hipMemcpyDeviceToHost));
+    if (nb_hist)
+        HIP_TRY(hipMemcpy2D(nb_hist, nw * 8, r->d_rung_nb, ((nw + 1) & ~(size_t)1) * 8, nw * 8, M, hipMemcpyDeviceToHost));
     return FC_OK;
 }
 

@@ -43,6 +43,30 @@ def owner(g: int, n_total: int, world: int) -> int:
     return g * world // n_total
 
 
+def shard_ladders(sizes, world: int, rank: int) -> Tuple[int, int, int, int]:
+    """Replica-exchange ladders over ranks: contiguous blocks of whole ladders, so that no ladder
+    straddles a rank (its swaps stay on one GPU).  ``sizes[l]`` is ladder l's rung count, the
+    ladders' chains being laid out one ladder after the other; ladder l goes to the rank that
+    :func:`owner` gives its first chain.  Returns ``(first_ladder, n_ladders, chain_offset,
+    n_chains)`` of ``rank``'s block (possibly empty).  ``chain_offset`` is the block's
+    ``chain_id_offset``: a ladder's random stream is keyed by its first chain's global id, so the
+    swaps do not depend on the sharding.  Per-rung statistics of ladders with the same layout
+    reduce over ranks with :func:`allreduce_sum`."""
+    if world <= 0 or not 0 <= rank < world:
+        raise ValueError("bad world/rank")
+    sz = np.asarray(sizes, dtype=np.int64).reshape(-1)
+    if sz.size == 0 or (sz <= 0).any():
+        raise ValueError("every ladder needs at least one rung")
+    start = np.concatenate([[0], np.cumsum(sz)])
+    own = start[:-1] * world // start[-1]
+    mine = np.nonzero(own == rank)[0]
+    if mine.size == 0:
+        lo = int(np.searchsorted(own, rank))
+        return lo, 0, int(start[lo]), 0
+    lo, hi = int(mine[0]), int(mine[-1]) + 1
+    return lo, hi - lo, int(start[lo]), int(start[hi] - start[lo])
+
+
 def group_aggregate(stats: Dict[str, np.ndarray], groups: np.ndarray, n_groups: int) -> np.ndarray:
     """[n_groups, len(AGG_FIELDS)] int64 sums of the per-chain statistics by group id."""
     out = np.zeros((n_groups, len(AGG_FIELDS)), dtype=np.int64)

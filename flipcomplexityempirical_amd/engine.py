@@ -535,6 +535,62 @@ class FlipRun:
         bounds = np.concatenate([[t0], ev["t"], [T + 1]]).astype(np.int64)
         return np.repeat(np.asarray(values)[:ev.size + 1], np.diff(bounds))
 
+    # ---- replica exchange (DESIGN.md "Replica exchange") ------------------------------
+    def set_ladders(self, ladders: Sequence[Sequence[int]], hist: bool = False) -> "FlipRun":
+        """``ladders``: lists of local chain indices, rung 0 first (``fc_run_set_ladders``; once
+        per run).  ``hist``: keep the |cut| / |B| histograms per rung too (needs FC_DIAG_HIST)."""
+        lad = [np.asarray(x, dtype=np.int32).reshape(-1) for x in ladders]
+        off = np.zeros(len(lad) + 1, dtype=np.int32)
+        off[1:] = np.cumsum([x.size for x in lad])
+        mem = np.ascontiguousarray(np.concatenate(lad) if lad else np.zeros(0, dtype=np.int32), dtype=np.int32)
+        check(_lib.load().fc_run_set_ladders(self.handle, len(lad), _p(off, ctypes.c_int32), _p(mem, ctypes.c_int32),
+                                             _lib.FC_LADDER_HIST if hist else 0), "fc_run_set_ladders")
+        self._ladder_off, self._ladder_hist = off, bool(hist)
+        return self
+
+    def exchange(self, parity: int = -1, stream: Optional[int] = None) -> "FlipRun":
+        """One exchange round between the ``steps`` launches it separates (asynchronous);
+        ``parity`` -1: the round counter's."""
+        check(_lib.load().fc_run_exchange(self.handle, int(parity), ctypes.c_void_p(stream) if stream else None),
+              "fc_run_exchange")
+        return self
+
+    def rungs(self):
+        """``(rung_of [n_chains], chain_at)``: the rung each chain holds (-1: no ladder) and, per
+        ladder, the chain at each rung."""
+        off = getattr(self, "_ladder_off", np.zeros(1, dtype=np.int32))
+        rung_of = np.zeros(self.n_chains, dtype=np.int32)
+        flat = np.zeros(max(int(off[-1]), 1), dtype=np.int32)
+        check(_lib.load().fc_run_read_rungs(self.handle, _p(rung_of, ctypes.c_int32), _p(flat, ctypes.c_int32)),
+              "fc_run_read_rungs")
+        return rung_of, [flat[off[i]:off[i + 1]].copy() for i in range(off.size - 1)]
+
+    def bases_now(self) -> np.ndarray:
+        """The base every chain runs at now (``fc_run_read_bases``)."""
+        out = np.zeros(self.n_chains, dtype=np.float64)
+        check(_lib.load().fc_run_read_bases(self.handle, _p(out, ctypes.c_double)), "fc_run_read_bases")
+        return out
+
+    def rung_stats(self) -> Dict[str, np.ndarray]:
+        """Per-slot statistics (slot = ladder offset + rung, in ``set_ladders`` order): the
+        ``fc_rung_stats`` fields as int64 arrays, ``ladder_off``, and with ``hist`` the per-slot
+        ``cut_hist`` / ``nb_hist`` (``fc_run_read_rung_stats``)."""
+        off = getattr(self, "_ladder_off", np.zeros(1, dtype=np.int32))
+        M = int(off[-1])
+        arr = (_lib.RungStats * max(M, 1))()
+        ch = nh = None
+        if getattr(self, "_ladder_hist", False):
+            ch = np.zeros((M, self.graph.n_edges + 1), dtype=np.int64)
+            nh = np.zeros((M, self.nb_width()), dtype=np.int64)
+        check(_lib.load().fc_run_read_rung_stats(self.handle, arr, _p(ch, ctypes.c_int64), _p(nh, ctypes.c_int64)),
+              "fc_run_read_rung_stats")
+        raw = np.ctypeslib.as_array(arr)[:M]
+        out = {f: np.array(raw[f]) for f, _ in _lib.RungStats._fields_}
+        out["ladder_off"] = off.copy()
+        if ch is not None:
+            out["cut_hist"], out["nb_hist"] = ch, nh
+        return out
+
     def diag_paths(self) -> Dict[str, int]:
         """The paths the memory-dependent diagnostics took (``fc_run_diag_paths``): tally-log
         entries per chain granted / asked for, and whether the last change-point call was staged."""

@@ -399,6 +399,62 @@ int fc_host_unregister(void *ptr);
  * chains then continue bit for bit as if never interrupted.  Per-proposal traces are outputs: they restart empty after a restore. */
 int fc_run_checkpoint(fc_run *r, void *buf, int64_t cap, int64_t *len);
 int fc_run_restore(fc_run *r, const void *buf, int64_t len);
+/* ---- replica exchange (parallel tempering) between chains of one run ---------------------- */
+/* No reference counterpart: the reference runs one chain per (base, tolerance) and shows that it
+ * mixes torpidly away from base 1; this is the standard remedy, defined here (DESIGN.md "Replica
+ * exchange").  A ladder is an ordered list of local chain indices, rung 0 first; a chain is in at
+ * most one ladder and chains in none are never touched.  Replicas keep their state, draw counter
+ * and accumulators; what moves between the chains of a ladder is the temperature (the base, i.e.
+ * the chain's acceptance thresholds).  Replica x at rung r (base b_r) and y at rung r + 1 swap
+ * with probability min(1, (b_r / b_{r+1}) ** (|cut_x| - |cut_y|)), which preserves the product of
+ * the rungs' stationary laws.  The uniform of the pair with lower rung r in round t is
+ * mant53(x0, x1) of Philox4x32-10(ctr = (t, r, G, 4), key = seed), G the global id
+ * (chain_id_offset + index) of the ladder's first-listed chain: no dependence on the sharding.
+ *
+ * fc_run_set_ladders: ladder l lists members[ladder_off[l] .. ladder_off[l + 1] - 1]
+ * (ladder_off[0] = 0); "slot" ladder_off[l] + r below is rung r of ladder l.  Callable once,
+ * before or between launches (what a chain accumulated before counts for its initial rung).
+ * FC_ERR_UNSUPPORTED for ReCom runs and accept kinds other than FC_ACCEPT_CUT (and graphs with
+ * 2^17 or more edges); FC_ERR_ARG for an index out of range, a chain listed twice, members of one
+ * ladder with different population bounds (bounds are never swapped), a non-positive base,
+ * unknown flags, FC_LADDER_HIST without FC_DIAG_HIST, or a second call; FC_ERR_NOMEM when the
+ * FC_LADDER_HIST buffers (a snapshot of both histograms and one row pair per slot) do not fit. */
+#define FC_LADDER_HIST 0x1u      /* keep the |cut| and |B| histograms per rung as well           */
+int fc_run_set_ladders(fc_run *r, int32_t n_ladders, const int32_t *ladder_off, const int32_t *members,
+                       uint32_t flags);
+/* One exchange round, asynchronous on hip_stream (NULL = the run's stream; use the stream of the
+ * fc_run_steps calls it separates): every ladder chain's sums since the last round are attributed
+ * to the rung it held, then the pairs (r, r + 1) with r = parity (mod 2) are tried; parity -1
+ * means (round counter & 1).  The round counter starts at 0 and advances by one per call.
+ * FC_ERR_ARG without ladders or for another parity. */
+int fc_run_exchange(fc_run *r, int32_t parity, void *hip_stream);
+/* rung_of [n_chains]: the rung each chain holds now (-1: in no ladder); chain_at [members]: the
+ * chain at each slot.  Either may be NULL.  Synchronises. */
+int fc_run_read_rungs(fc_run *r, int32_t *rung_of, int32_t *chain_at);
+/* bases [n_chains]: the base each chain runs at now (also valid without ladders). */
+int fc_run_read_bases(fc_run *r, double *bases);
+/* Per-slot (per-temperature) statistics: the streaming sums of whichever replicas held the slot,
+ * each launch's deltas going to the rung held during it (the initial yield to the initial rung),
+ * and the swaps tried / accepted of the pair (slot, slot + 1). */
+typedef struct fc_rung_stats {
+    int64_t steps, proposals, draws, accepted, inv_contig, inv_pop;
+    int64_t sum_cut, sum_nb, sum_wait, sum_cut2, sum_nb2;   /* as in fc_chain_stats              */
+    int64_t swaps_tried, swaps_accepted;                    /* pair (this slot, next slot)       */
+} fc_rung_stats;
+/* Attributes what is outstanding (no swap, no round counted), then copies: out [members];
+ * cut_hist [members * (E + 1)] and nb_hist [members * fc_run_nb_width] with FC_LADDER_HIST (NULL
+ * to skip; FC_ERR_ARG when asked for without it). */
+int fc_run_read_rung_stats(fc_run *r, fc_rung_stats *out, int64_t *cut_hist, int64_t *nb_hist);
+/* The U53 threshold of one swap decision, by the code the device runs: the pair of rungs with
+ * bases (b_lo_rung, b_hi_rung) and d = |cut| of the lower rung's replica - |cut| of the upper's
+ * swaps iff mant53 < *t.  2^53 when (b_lo_rung / b_hi_rung) ** d >= 1; otherwise
+ * ceil(p 2^53), p the product over the set bits j of |d| (ascending) of pow(qq, 2^j),
+ * qq = min(b) / max(b), cut to 0 once below 2^-64.  Pure host function; |d| < 2^17. */
+int fc_ladder_swap_threshold(double b_lo_rung, double b_hi_rung, int32_t d, uint64_t *t);
+/* Checkpoints of a run with ladders append the rung map, the snapshots, the per-slot sums and
+ * histograms, the swap counters and the round counter, and carry a hash of the ladder layout; they
+ * restore only into a run with the same ladders set (FC_ERR_ARG otherwise, also for a run
+ * without ladders).  Blobs of runs without ladders are unchanged. */
 /* Name of the last launched flip-kernel instance, as rocprofv3 spells it. */
 int fc_run_kernel_name(const fc_run *r, char *buf, int32_t cap);
 int32_t fc_run_n_chains(const fc_run *r);
