@@ -22,8 +22,12 @@ CSRC = os.path.join(PKG, "csrc")
 VARIANT = os.environ.get("FC_LIB_VARIANT", "")
 VARIANT_FLAGS = {"prof": "-DFC_PHASE_PROF", "sync": "-DFC_PHASE_SYNC"}
 LIB = os.environ.get("FC_LIB_OUT") or os.path.join(PKG, f"libflipchain_{VARIANT}.so" if VARIANT else "libflipchain.so")
-SOURCES = ["fc_flip2.hip", "fc_deal.hip", "fc_kernels.hip", "fc_series.hip", "fc_recom.hip", "fc_exchange.hip", "fc_capi.cpp", "fc_graph.cpp"]
-HEADERS = ["fc_internal.h", "fc_philox.h", "fc_device.h", "fc_ring.h", "fc_ladder.h", os.path.join("..", "..", "include", "flipchain.h")]
+SOURCES = ["fc_flip2.hip", "fc_deal.hip", "fc_kernels.hip", "fc_series.hip", "fc_recom.hip", "fc_exchange.hip",
+           "fc_capi.cpp", "fc_plan.cpp", "fc_ckpt.cpp", "fc_tempering.cpp", "fc_readout.cpp", "fc_graph.cpp"]
+HEADERS = ["fc_internal.h", "fc_philox.h", "fc_device.h", "fc_ring.h", "fc_ladder.h", "fc_plan.h", "fc_run.h",
+           os.path.join("..", "..", "include", "flipchain.h")]
+# plain C++ that includes no HIP header: compiled as such (tests/sanitize builds it with g++)
+HOST_ONLY = {"fc_plan.cpp"}
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("FC_OFFLOAD_ARCH", "gfx950")
 
@@ -91,7 +95,9 @@ def build(force: bool = False, verbose: bool = False) -> str:
         objs = [os.path.join(tmp, os.path.splitext(src)[0] + ".o") for src in SOURCES]
         jobs = int(os.environ.get("MAX_JOBS", "0")) or min(len(SOURCES), os.cpu_count() or 1, 8)
         with ThreadPoolExecutor(max_workers=jobs) as pool:
-            futs = [pool.submit(_run, [HIPCC, *flags, "-c", "-o", obj, os.path.join(CSRC, src)], verbose)
+            host = ["-x", "c++"] + [f for f in flags if not f.startswith("--offload-arch")]
+            futs = [pool.submit(_run, [HIPCC, *(host if src in HOST_ONLY else flags), "-c", "-o", obj,
+                                       os.path.join(CSRC, src)], verbose)
                     for src, obj in zip(SOURCES, objs)]
             for f in futs:
                 f.result()

@@ -1,0 +1,543 @@
+// Readouts of a run and the series drivers (fc_series.hip).
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "fc_run.h"
+
+namespace {
+
+// a chain whose event log ran past event_cap has no series to evaluate
+int check_event_overflow(const fc_run *r, const char *who, int32_t chain, const fc::ChainScalars &s) {
+    if (s.ev_len > r->ev_cap)
+        return fail(FC_ERR_ARG, std::string(who) + ": chain " + std::to_string(chain) +
+                                    " overflowed event_cap; reset the series window more often");
+    return FC_OK;
+}
+
+int check_frame_edges(const char *who, int32_t n, int32_t n_frame, const int32_t *frame_u, const int32_t *frame_v) {
+    for (int32_t j = 0; j < n_frame; ++j)
+        if (frame_u[j] < 0 || frame_u[j] >= n || frame_v[j] < 0 || frame_v[j] >= n || frame_u[j] == frame_v[j])
+            return fail(FC_ERR_ARG, std::string(who) + ": frame edge " + std::to_string(j) + " out of range");
+    return FC_OK;
+}
+
+// the frame kernels' toggle tables: tog_idx[node] is the node's row in tog[.][4] (a 256-bit mask
+// of the frame edges incident to it) or -1
+void build_toggles(int32_t n, int32_t n_frame, const int32_t *frame_u, const int32_t *frame_v,
+                   std::vector<int32_t> &tog_idx, std::vector<uint64_t> &tog) {
+    tog_idx.assign(n, -1);
+    tog.clear();
+    for (int32_t j = 0; j < n_frame; ++j) {
+        const int32_t ends[2] = {frame_u[j], frame_v[j]};
+        for (int32_t x : ends) {
+            if (tog_idx[x] < 0) {
+                tog_idx[x] = (int32_t)(tog.size() / 4);
+                tog.insert(tog.end(), 4, 0);
+            }
+            tog[(size_t)tog_idx[x] * 4 + (j >> 6)] |= uint64_t(1) << (j & 63);
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int fc_run_read_stats(fc_run *r, fc_chain_stats *out) {
+    if (!r || !out) return fail(FC_ERR_ARG, "fc_run_read_stats: null argument");
+    std::vector<fc::ChainScalars> sc;
+    if (int rc = download_scalars(r, 0, r->n_chains, sc)) return rc;
+    for (int32_t c = 0; c < r->n_chains; ++c) {
+        const fc::ChainScalars &s = sc[c];
+        fc_chain_stats &o = out[c];
+        o.steps = s.steps;
+        o.proposals = s.proposals;
+        o.draws = (int64_t)s.draw;
+        o.accepted = s.accepted;
+        o.inv_contig = s.inv_contig;
+        o.inv_pop = s.inv_pop;
+        o.sum_cut = s.sum_cut;
+        o.sum_nb = s.sum_nb;
+        o.sum_wait = s.sum_wait;
+        o.sum_cut2 = s.sum_cut2;
+        o.sum_nb2 = s.sum_nb2;
+        o.wait_cur = s.wait_cur;
+        o.bfs_calls = s.bfs_calls;
+        o.bfs_levels = s.bfs_levels;
+        o.cut = s.cut;
+        o.nb = s.nb;
+        o.last_flip = s.last_flip;
+        o.stuck = s.stuck;
+        o.hit_time = s.hit_time;
+        o.events = s.ev_len;
+        o.series_t0 = s.ser_t0;
+        o.series_cut0 = s.ser_cut0;
+        o.series_nb0 = s.ser_nb0;
+    }
+    return FC_OK;
+}
+
+int fc_run_read_state(fc_run *r, int8_t *assign_out) {
+    if (!r || !assign_out) return fail(FC_ERR_ARG, "fc_run_read_state: null argument");
+    if (int rc = fc_run_sync(r)) return rc;
+    std::vector<int8_t> a((size_t)r->n_chains * r->npad);
+    HIP_TRY(hipMemcpy(a.data(), r->d_assign, a.size(), hipMemcpyDeviceToHost));
+    for (int32_t c = 0; c < r->n_chains; ++c)
+        std::memcpy(assign_out + (size_t)c * r->g.n, &a[(size_t)c * r->npad], r->g.n);
+    return FC_OK;
+}
+
+int fc_run_read_pops(fc_run *r, int64_t *pops_out) {
+    if (!r || !pops_out) return fail(FC_ERR_ARG, "fc_run_read_pops: null argument");
+    const int k = r->p.k;
+    if (k == 2) {
+        std::vector<fc::ChainScalars> sc;
+        if (int rc = download_scalars(r, 0, r->n_chains, sc)) return rc;
+        for (int32_t c = 0; c < r->n_chains; ++c) {
+            pops_out[2 * c] = sc[c].pops[0];
+            pops_out[2 * c + 1] = sc[c].pops[1];
+        }
+    } else {
+        if (int rc = fc_run_sync(r)) return rc;
+        std::vector<int32_t> pk((size_t)r->n_chains * fc::kMaxKGeneral);
+        HIP_TRY(hipMemcpy(pk.data(), r->d_popk, pk.size() * 4, hipMemcpyDeviceToHost));
+        for (int32_t c = 0; c < r->n_chains; ++c)
+            for (int d = 0; d < k; ++d) pops_out[(size_t)c * k + d] = pk[(size_t)c * fc::kMaxKGeneral + d];
+    }
+    return FC_OK;
+}
+
+int fc_run_read_trace(fc_run *r, int32_t chain, fc_record *out, int64_t cap, int64_t *len) {
+    if (!r || !out || !len) return fail(FC_ERR_ARG, "fc_run_read_trace: null argument");
+    if (chain < 0 || chain >= r->p.trace_chains) return fail(FC_ERR_ARG, "fc_run_read_trace: chain is not traced");
+    std::vector<fc::ChainScalars> sc;
+    if (int rc = download_scalars(r, chain, 1, sc)) return rc;
+    const fc::ChainScalars &s = sc[0];
+    const int64_t n = std::min<int64_t>({s.trace_len, r->p.trace_cap, cap});
+    HIP_TRY(hipMemcpy(out, r->d_trace + (size_t)chain * r->p.trace_cap, (size_t)n * sizeof(fc_record),
+                      hipMemcpyDeviceToHost));
+    *len = s.trace_len;
+    return FC_OK;
+}
+
+int fc_run_read_recom_trace(fc_run *r, int32_t chain, fc_recom_record *out, int64_t cap, int64_t *len) {
+    if (!r || !out || !len) return fail(FC_ERR_ARG, "fc_run_read_recom_trace: null argument");
+    if (r->p.proposal != FC_PROPOSE_RECOM) return fail(FC_ERR_ARG, "fc_run_read_recom_trace: not a recom run");
+    if (chain < 0 || chain >= r->p.trace_chains) return fail(FC_ERR_ARG, "fc_run_read_recom_trace: chain is not traced");
+    std::vector<fc::ChainScalars> sc;
+    if (int rc = download_scalars(r, chain, 1, sc)) return rc;
+    const fc::ChainScalars &s = sc[0];
+    const int64_t n = std::min<int64_t>({s.trace_len, r->p.trace_cap, cap});
+    static_assert(sizeof(fc_recom_record) == sizeof(fc_record), "trace slots are shared");
+    HIP_TRY(hipMemcpy(out, (const fc_recom_record *)r->d_trace.get() + (size_t)chain * r->p.trace_cap,
+                      (size_t)n * sizeof(fc_recom_record), hipMemcpyDeviceToHost));
+    *len = s.trace_len;
+    return FC_OK;
+}
+
+int fc_run_trace_reset(fc_run *r) {
+    if (!r) return fail(FC_ERR_ARG, "fc_run_trace_reset: null run");
+    std::vector<fc::ChainScalars> sc;
+    if (int rc = download_scalars(r, 0, r->n_chains, sc)) return rc;
+    for (auto &s : sc) s.trace_len = 0;
+    HIP_TRY(hipMemcpy(r->d_sc, sc.data(), sc.size() * sizeof(sc[0]), hipMemcpyHostToDevice));
+    return FC_OK;
+}
+
+int fc_run_read_events(fc_run *r, int32_t chain, fc_event *out, int64_t cap, int64_t *len) {
+    if (!r || !len || (cap > 0 && !out)) return fail(FC_ERR_ARG, "fc_run_read_events: null argument");
+    if (!r->d_events) return fail(FC_ERR_ARG, "fc_run_read_events: FC_DIAG_SERIES not enabled");
+    if (chain < 0 || chain >= r->n_chains) return fail(FC_ERR_ARG, "fc_run_read_events: chain out of range");
+    std::vector<fc::ChainScalars> sc;
+    if (int rc = download_scalars(r, chain, 1, sc)) return rc;
+    const fc::ChainScalars &s = sc[0];
+    const int64_t n = std::min<int64_t>({s.ev_len, r->ev_cap, cap});
+    if (n > 0)
+        HIP_TRY(hipMemcpy(out, r->d_events + (size_t)chain * r->ev_cap, (size_t)n * sizeof(fc_event),
+                          hipMemcpyDeviceToHost));
+    *len = s.ev_len;
+    return FC_OK;
+}
+
+int fc_run_series_reset(fc_run *r) {
+    if (!r) return fail(FC_ERR_ARG, "fc_run_series_reset: null run");
+    std::vector<fc::ChainScalars> sc;
+    if (int rc = download_scalars(r, 0, r->n_chains, sc)) return rc;
+    for (auto &s : sc) {
+        s.ev_len = 0;
+        s.ser_t0 = s.steps;
+        s.ser_cut0 = s.cut;
+        s.ser_nb0 = s.nb;
+    }
+    HIP_TRY(hipMemcpy(r->d_sc, sc.data(), sc.size() * sizeof(sc[0]), hipMemcpyHostToDevice));
+    if (r->d_ser_a0)
+        HIP_TRY(hipMemcpy(r->d_ser_a0, r->d_assign, (size_t)r->n_chains * r->npad, hipMemcpyDeviceToDevice));
+    return FC_OK;
+}
+
+int fc_run_autocorr(fc_run *r, const int32_t *lags, int32_t nlags, int64_t *lag_sums, double *acf) {
+    if (!r || !lags || nlags <= 0 || !lag_sums) return fail(FC_ERR_ARG, "fc_run_autocorr: null argument");
+    if (!r->d_events) return fail(FC_ERR_ARG, "fc_run_autocorr: FC_DIAG_SERIES not enabled");
+    for (int32_t j = 0; j < nlags; ++j)
+        if (lags[j] < 0) return fail(FC_ERR_ARG, "fc_run_autocorr: negative lag");
+    const int32_t C = r->n_chains;
+    std::vector<fc::ChainScalars> sc;
+    if (int rc = download_scalars(r, 0, C, sc)) return rc;
+    std::vector<int64_t> ev_len(C), t0(C), len(C);
+    std::vector<int32_t> cut0(C);
+    int64_t max_len = 0;
+    for (int32_t c = 0; c < C; ++c) {
+        if (int rc = check_event_overflow(r, "fc_run_autocorr", c, sc[c])) return rc;
+        ev_len[c] = sc[c].ev_len;
+        t0[c] = sc[c].ser_t0;
+        cut0[c] = sc[c].ser_cut0;
+        len[c] = sc[c].steps - sc[c].ser_t0 + 1;  // yields t0 .. steps
+        max_len = std::max(max_len, len[c]);
+    }
+    // lag 0 is always evaluated first: it yields the window totals Sx = H_0 and Sxx = P_0
+    std::vector<int32_t> lg(nlags + 1);
+    lg[0] = 0;
+    std::copy(lags, lags + nlags, lg.begin() + 1);
+    const int32_t nl = nlags + 1;
+    // device scratch: metadata + dense series for a batch of chains (<= 1 GiB)
+    const int64_t stride = (max_len + 7) & ~int64_t(7);
+    const int32_t batch = (int32_t)std::max<int64_t>(1, std::min<int64_t>({C, 65535, (int64_t(1) << 29) / stride}));
+    DevBuf<int64_t> d_meta;  // ev_len, t0, len: [C] each
+    DevBuf<int32_t> d_cut0, d_lags;
+    DevBuf<uint16_t> d_x;
+    DevBuf<unsigned long long> d_sums;
+    int q;
+    if ((q = d_meta.alloc((size_t)3 * C))) return q;
+    if ((q = d_cut0.alloc((size_t)C))) return q;
+    if ((q = d_lags.alloc((size_t)nl))) return q;
+    if ((q = d_x.alloc((size_t)batch * stride))) return q;
+    if ((q = d_sums.alloc((size_t)C * nl * 3))) return q;
+    HIP_TRY(hipMemcpy(d_meta, ev_len.data(), (size_t)C * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_meta + C, t0.data(), (size_t)C * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_meta + 2 * C, len.data(), (size_t)C * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_cut0, cut0.data(), (size_t)C * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_lags, lg.data(), (size_t)nl * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemsetAsync(d_sums, 0, (size_t)C * nl * 3 * 8, r->stream));
+    for (int32_t c0 = 0; c0 < C; c0 += batch) {
+        const int32_t nc = std::min(batch, C - c0);
+        int e = fc::launch_series_expand(r->d_events, r->ev_cap, d_meta, d_meta + C, d_cut0, d_meta + 2 * C, c0,
+                                         nc, stride, max_len, d_x, r->stream);
+        if (e) return fail(FC_ERR_HIP, std::string("series expand: ") + hipGetErrorString((hipError_t)e));
+        e = fc::launch_series_lagsums(d_x, d_meta + 2 * C, c0, nc, stride, max_len, d_lags, nl, d_sums,
+                                      r->stream);
+        if (e) return fail(FC_ERR_HIP, std::string("series lag sums: ") + hipGetErrorString((hipError_t)e));
+    }
+    std::vector<int64_t> sums((size_t)C * nl * 3);
+    HIP_TRY(hipMemcpyAsync(sums.data(), d_sums, sums.size() * 8, hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    for (int32_t c = 0; c < C; ++c) {
+        const int64_t *s0 = &sums[(size_t)c * nl * 3];
+        const __int128 Sxx = s0[0], Sx = s0[1], T = len[c];
+        for (int32_t j = 0; j < nlags; ++j) {
+            const int64_t *s = s0 + 3 * (j + 1);
+            lag_sums[(size_t)c * nlags + j] = s[0];
+            if (!acf) continue;
+            const __int128 L = lags[j];
+            double v = 0.0;
+            if (L < T) {
+                // T^2 * sum_{t < T-L} (x_t - m)(x_{t+L} - m), m = Sx / T, in exact integers
+                const __int128 num = T * T * (__int128)s[0] - T * Sx * ((__int128)s[1] + s[2]) + (T - L) * Sx * Sx;
+                const __int128 den = T * (T * Sxx - Sx * Sx);
+                if (den != 0) v = (double)num / (double)den;
+            }
+            acf[(size_t)c * nlags + j] = v;
+        }
+    }
+    return FC_OK;
+}
+
+int fc_run_frame_series(fc_run *r, int32_t c0, int32_t nc, int32_t n_frame, const int32_t *frame_u,
+                        const int32_t *frame_v, const double *mid_xy, double cx, double cy, int64_t cap,
+                        double *slope, double *angle, int32_t *n_cut, int64_t *len) {
+    if (!r || !frame_u || !frame_v || !mid_xy || !slope || !angle || !n_cut || !len)
+        return fail(FC_ERR_ARG, "fc_run_frame_series: null argument");
+    if (!r->d_events) return fail(FC_ERR_ARG, "fc_run_frame_series: FC_DIAG_SERIES not enabled");
+    if (r->p.k != 2)
+        return fail(FC_ERR_UNSUPPORTED, "fc_run_frame_series: the frame series follows k = 2 flips (the reference "
+                                        "computes boundary_slope only in its two-district drivers)");
+    if (c0 < 0 || nc < 0 || c0 + nc > r->n_chains) return fail(FC_ERR_ARG, "fc_run_frame_series: chain range");
+    if (n_frame < 0 || n_frame > 256) return fail(FC_ERR_UNSUPPORTED, "fc_run_frame_series: at most 256 frame edges");
+    const int32_t n = r->g.n;
+    if (int rc = check_frame_edges("fc_run_frame_series", n, n_frame, frame_u, frame_v)) return rc;
+    std::vector<int32_t> tog_idx;
+    std::vector<uint64_t> tog;
+    build_toggles(n, n_frame, frame_u, frame_v, tog_idx, tog);
+    if (nc == 0) return FC_OK;
+    std::vector<fc::ChainScalars> sc;
+    if (int rc = download_scalars(r, c0, nc, sc)) return rc;
+    std::vector<int64_t> ev_len(r->n_chains, 0);
+    for (int32_t i = 0; i < nc; ++i) {
+        if (int rc = check_event_overflow(r, "fc_run_frame_series", c0 + i, sc[i])) return rc;
+        if (sc[i].ev_len + 1 > cap)
+            return fail(FC_ERR_ARG, "fc_run_frame_series: cap < events + 1 for chain " + std::to_string(c0 + i));
+        ev_len[c0 + i] = sc[i].ev_len;
+        len[i] = sc[i].ev_len + 1;
+    }
+    DevBuf<int32_t> d_fuv, d_tidx;
+    DevBuf<int64_t> d_len;
+    DevBuf<uint64_t> d_tog;
+    DevBuf<double> d_mid;
+    int q;
+    const size_t outn = (size_t)nc * cap;
+    if ((q = d_fuv.alloc((size_t)2 * std::max(n_frame, 1)))) return q;
+    if ((q = d_tidx.alloc((size_t)n))) return q;
+    if ((q = d_tog.alloc(std::max<size_t>(tog.size(), 4)))) return q;
+    if ((q = d_mid.alloc((size_t)2 * std::max(n_frame, 1)))) return q;
+    if ((q = d_len.alloc((size_t)r->n_chains))) return q;
+    // the large outputs are kept by the run (chunked callers ask for similar sizes)
+    if ((q = r->d_fs_out.grow(2 * outn))) return q;
+    if ((q = r->d_fs_cnt.grow(outn))) return q;
+    double *const d_out = r->d_fs_out;
+    int32_t *const d_cnt = r->d_fs_cnt;
+    if (n_frame) {
+        HIP_TRY(hipMemcpy(d_fuv, frame_u, (size_t)n_frame * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_fuv + n_frame, frame_v, (size_t)n_frame * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_mid, mid_xy, (size_t)n_frame * 16, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_tog, tog.data(), tog.size() * 8, hipMemcpyHostToDevice));
+    }
+    HIP_TRY(hipMemcpy(d_tidx, tog_idx.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_len, ev_len.data(), ev_len.size() * 8, hipMemcpyHostToDevice));
+    int e = fc::launch_frame_series(r->d_ser_a0, r->npad, r->d_events, r->ev_cap, d_len, c0, nc, n_frame, d_fuv,
+                                    d_fuv + n_frame, d_mid, cx, cy, d_tidx, d_tog, (int32_t)(tog.size() / 4), n,
+                                    cap, d_out, d_out + outn,
+                                    d_cnt, r->stream);
+    if (e) return fail(FC_ERR_HIP, std::string("frame series: ") + hipGetErrorString((hipError_t)e));
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    HIP_TRY(hipMemcpy(slope, d_out, outn * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(angle, d_out + outn, outn * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(n_cut, d_cnt, outn * 4, hipMemcpyDeviceToHost));
+    return FC_OK;
+}
+
+int fc_run_frame_series_changes(fc_run *r, int32_t c0, int32_t nc, int32_t n_frame, const int32_t *frame_u,
+                                const int32_t *frame_v, const double *mid_xy, double cx, double cy, int64_t cap,
+                                int64_t *offsets, int64_t *t, double *slope, double *angle) {
+    if (!r || !frame_u || !frame_v || !mid_xy || !offsets)
+        return fail(FC_ERR_ARG, "fc_run_frame_series_changes: null argument");
+    const bool query = !t && !slope && !angle;
+    if (!query && (!t || !slope || !angle)) return fail(FC_ERR_ARG, "fc_run_frame_series_changes: null output");
+    if (!r->d_events) return fail(FC_ERR_ARG, "fc_run_frame_series_changes: FC_DIAG_SERIES not enabled");
+    if (r->p.k != 2) return fail(FC_ERR_UNSUPPORTED, "fc_run_frame_series_changes: k = 2 runs only");
+    if (c0 < 0 || nc < 0 || c0 + nc > r->n_chains) return fail(FC_ERR_ARG, "fc_run_frame_series_changes: chain range");
+    if (n_frame < 0 || n_frame > 256)
+        return fail(FC_ERR_UNSUPPORTED, "fc_run_frame_series_changes: at most 256 frame edges");
+    const int32_t n = r->g.n;
+    if (int rc = check_frame_edges("fc_run_frame_series_changes", n, n_frame, frame_u, frame_v)) return rc;
+    offsets[0] = 0;
+    if (nc == 0) return FC_OK;
+    std::vector<fc::ChainScalars> sc;
+    if (int rc = download_scalars(r, c0, nc, sc)) return rc;
+    std::vector<int64_t> ev_len(nc), t0(nc);
+    for (int32_t i = 0; i < nc; ++i) {
+        if (int rc = check_event_overflow(r, "fc_run_frame_series_changes", c0 + i, sc[i])) return rc;
+        ev_len[i] = sc[i].ev_len;
+        t0[i] = sc[i].ser_t0;
+    }
+    int q;
+    // the frame tables: uploaded when the frame differs from the last call's
+    uint64_t h = fnv1a(fc::kFnvBasis, &n_frame, sizeof n_frame);
+    h = fnv1a(h, frame_u, (size_t)n_frame * 4);
+    h = fnv1a(h, frame_v, (size_t)n_frame * 4);
+    h = fnv1a(h, mid_xy, (size_t)n_frame * 16);
+    if (!r->d_fc_fuv || h != r->fc_frame_hash) {
+        std::vector<int32_t> tog_idx;
+        std::vector<uint64_t> tog;
+        build_toggles(n, n_frame, frame_u, frame_v, tog_idx, tog);
+        if ((q = r->d_fc_fuv.alloc((size_t)2 * 256))) return q;
+        if ((q = r->d_fc_tidx.alloc((size_t)n))) return q;
+        if ((q = r->d_fc_tog.alloc((size_t)4 * 512))) return q;
+        if ((q = r->d_fc_mid.alloc((size_t)2 * 256))) return q;
+        if (n_frame) {
+            HIP_TRY(hipMemcpy(r->d_fc_fuv, frame_u, (size_t)n_frame * 4, hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(r->d_fc_fuv + n_frame, frame_v, (size_t)n_frame * 4, hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(r->d_fc_mid, mid_xy, (size_t)n_frame * 16, hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(r->d_fc_tog, tog.data(), tog.size() * 8, hipMemcpyHostToDevice));
+        }
+        HIP_TRY(hipMemcpy(r->d_fc_tidx, tog_idx.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+        r->fc_frame_hash = h;
+        r->fc_rows = (int32_t)(tog.size() / 4);
+    }
+    if (!r->d_fc_len) {
+        const size_t C = (size_t)r->n_chains;
+        if ((q = r->d_fc_len.alloc(C))) return q;
+        if ((q = r->d_fc_t0.alloc(C))) return q;
+        if ((q = r->d_fc_cnt.alloc(C))) return q;
+        if ((q = r->d_fc_off.alloc(C))) return q;
+        if ((q = r->d_fc_wcnt.alloc(C * fc::kFrameWaves))) return q;
+    }
+    // the kernels index the per-chain arrays by global chain id
+    HIP_TRY(hipMemcpyAsync(r->d_fc_len + c0, ev_len.data(), (size_t)nc * 8, hipMemcpyHostToDevice, r->stream));
+    HIP_TRY(hipMemcpyAsync(r->d_fc_t0 + c0, t0.data(), (size_t)nc * 8, hipMemcpyHostToDevice, r->stream));
+    int32_t *const d_fuv = r->d_fc_fuv;
+    // one pass (count and write together) into per-wave staging ranges when they fit a tenth of
+    // the free device memory: sized by event_cap, kept by the run
+    const int64_t nk = (r->ev_cap + 63) / 64;
+    const int64_t sub = 64 * ((nk + fc::kFrameWaves - 1) / fc::kFrameWaves) + 1;
+    const int64_t stage_cap = sub * fc::kFrameWaves;
+    bool staged = false;
+    if (!query && !(r->p.flags & FC_FLAG_SERIES_TWO_PASS)) {
+        const size_t want = (size_t)r->n_chains * (size_t)stage_cap;
+        if (2 * want > r->d_st_sa.capacity()) {  // (d_st_sa is allocated last: it vouches for d_st_t)
+            size_t free_b = 0, total_b = 0;
+            HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+            if (want * 24 <= free_b / 10) {
+                r->d_st_t.release();  // both go before either comes back
+                r->d_st_sa.release();
+                if ((q = r->d_st_t.grow(want))) return q;
+                if ((q = r->d_st_sa.grow(2 * want))) return q;
+            }
+        }
+        staged = 2 * want <= r->d_st_sa.capacity();
+    }
+    if (!query) r->series_staged = staged ? 1 : 0;
+    const size_t stn = r->d_st_sa.capacity() / 2;  // staging: slope at d_st_sa, angle at d_st_sa + stn
+    int e;
+    if (staged)
+        e = fc::launch_frame_stage(r->d_ser_a0, r->npad, r->d_events, r->ev_cap, r->d_fc_len, c0, nc, n_frame, d_fuv,
+                                   d_fuv + n_frame, r->d_fc_mid, cx, cy, r->d_fc_tidx, r->d_fc_tog, r->fc_rows, n,
+                                   r->d_fc_t0, r->d_fc_cnt, stage_cap, r->d_st_t, r->d_st_sa, r->d_st_sa + stn,
+                                   r->d_fc_wcnt, r->stream);
+    else  // pass 1: change points per chain -> offsets
+        e = fc::launch_frame_changes(r->d_ser_a0, r->npad, r->d_events, r->ev_cap, r->d_fc_len, c0, nc, n_frame, d_fuv,
+                                     d_fuv + n_frame, r->d_fc_mid, cx, cy, r->d_fc_tidx, r->d_fc_tog, r->fc_rows, n,
+                                     r->d_fc_t0, r->d_fc_cnt, nullptr, nullptr, nullptr, nullptr, r->d_fc_wcnt, r->stream);
+    if (e) return fail(FC_ERR_HIP, std::string(staged ? "frame changes (stage): " : "frame changes (count): ") +
+                                       hipGetErrorString((hipError_t)e));
+    std::vector<int64_t> cnt(nc);
+    HIP_TRY(hipMemcpyAsync(cnt.data(), r->d_fc_cnt, (size_t)nc * 8, hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    for (int32_t i = 0; i < nc; ++i) offsets[i + 1] = offsets[i] + cnt[i];
+    const int64_t total = offsets[nc];
+    if (query) return FC_OK;
+    if (cap < total)  // offsets are filled: the caller can size its buffers and call again
+        return fail(FC_ERR_ARG, "fc_run_frame_series_changes: cap " + std::to_string(cap) + " < " +
+                                    std::to_string(total) + " change points (offsets[nc])");
+    if (2 * (size_t)total > r->d_fc_sa.capacity()) {  // (d_fc_sa is allocated last: it vouches for d_fc_t)
+        const size_t want = (size_t)total + (size_t)total / 4 + 1024;  // headroom: one allocation per run
+        r->d_fc_t.release();  // both go before either comes back
+        r->d_fc_sa.release();
+        if ((q = r->d_fc_t.grow(want))) return q;
+        if ((q = r->d_fc_sa.grow(2 * want))) return q;
+    }
+    // pass 2: (t, slope, angle) at the offsets, then one copy per array
+    HIP_TRY(hipMemcpyAsync(r->d_fc_off, offsets, (size_t)nc * 8, hipMemcpyHostToDevice, r->stream));
+    double *const d_sl = r->d_fc_sa, *const d_an = r->d_fc_sa + r->d_fc_sa.capacity() / 2;
+    if (staged)  // the staged ranges packed at the offsets
+        e = fc::launch_frame_compact(nc, stage_cap, r->d_st_t, r->d_st_sa, r->d_st_sa + stn, r->d_fc_wcnt, r->d_fc_off,
+                                     r->d_fc_t, d_sl, d_an, r->stream);
+    else
+        e = fc::launch_frame_changes(r->d_ser_a0, r->npad, r->d_events, r->ev_cap, r->d_fc_len, c0, nc, n_frame, d_fuv,
+                                     d_fuv + n_frame, r->d_fc_mid, cx, cy, r->d_fc_tidx, r->d_fc_tog, r->fc_rows, n,
+                                     r->d_fc_t0, r->d_fc_cnt, r->d_fc_off, r->d_fc_t, d_sl, d_an, r->d_fc_wcnt, r->stream);
+    if (e) return fail(FC_ERR_HIP, std::string("frame changes (write): ") + hipGetErrorString((hipError_t)e));
+    HIP_TRY(hipMemcpyAsync(t, r->d_fc_t, (size_t)total * 8, hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(hipMemcpyAsync(slope, d_sl, (size_t)total * 8, hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(hipMemcpyAsync(angle, d_an, (size_t)total * 8, hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    return FC_OK;
+}
+
+int fc_run_read_hist(fc_run *r, int64_t *cut_hist, int64_t *nb_hist) {
+    if (!r || !cut_hist || !nb_hist) return fail(FC_ERR_ARG, "fc_run_read_hist: null argument");
+    if (!r->d_cut_hist) return fail(FC_ERR_ARG, "fc_run_read_hist: FC_DIAG_HIST not enabled");
+    if (int rc = fc_run_sync(r)) return rc;
+    HIP_TRY(hipMemcpy(cut_hist, r->d_cut_hist, (size_t)r->n_chains * (r->g.n_edges + 1) * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(nb_hist, r->d_nb_hist, (size_t)r->n_chains * r->nb_w * 8, hipMemcpyDeviceToHost));
+    return FC_OK;
+}
+
+int fc_run_read_edges(fc_run *r, int64_t *cut_times) {
+    if (!r || !cut_times) return fail(FC_ERR_ARG, "fc_run_read_edges: null argument");
+    if (!r->d_edge_acc) return fail(FC_ERR_ARG, "fc_run_read_edges: FC_DIAG_EDGES not enabled");
+    const size_t E = r->g.n_edges, C = r->n_chains;
+    std::vector<int64_t> acc(C * E);
+    std::vector<int8_t> a(C * r->npad);
+    std::vector<fc::ChainScalars> sc;
+    if (int rc = download_scalars(r, 0, r->n_chains, sc)) return rc;
+    HIP_TRY(hipMemcpy(acc.data(), r->d_edge_acc, acc.size() * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(a.data(), r->d_assign, a.size(), hipMemcpyDeviceToHost));
+    for (size_t c = 0; c < C; ++c) {
+        const int8_t *ac = &a[c * r->npad];
+        const int64_t T = sc[c].steps + 1;  // yields so far
+        for (size_t e = 0; e < E; ++e) {
+            const bool is_cut = ac[r->g.eu[e]] != ac[r->g.ev[e]];
+            // the kernels add the yield at which e turns uncut and subtract the one at which it
+            // turns cut; an edge cut now is cut through the last yield
+            cut_times[c * E + e] = acc[c * E + e] + (is_cut ? T : 0);
+        }
+    }
+    return FC_OK;
+}
+
+int fc_run_read_flips(fc_run *r, int64_t *num_flips, int64_t *part_sum, int64_t *last_flipped) {
+    if (!r || !num_flips || !part_sum || !last_flipped) return fail(FC_ERR_ARG, "fc_run_read_flips: null argument");
+    if (!r->d_num_flips) return fail(FC_ERR_ARG, "fc_run_read_flips: FC_DIAG_FLIPS not enabled");
+    const size_t n = r->g.n, C = r->n_chains;
+    std::vector<int8_t> a(C * r->npad);
+    std::vector<fc::ChainScalars> sc;
+    if (int rc = download_scalars(r, 0, r->n_chains, sc)) return rc;
+    HIP_TRY(hipMemcpy(num_flips, r->d_num_flips, C * n * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(part_sum, r->d_part_sum, C * n * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(last_flipped, r->d_last_flipped, C * n * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(a.data(), r->d_assign, a.size(), hipMemcpyDeviceToHost));
+    const int64_t lsum = (int64_t)r->labels[0] + (int64_t)r->labels[1];
+    for (size_t c = 0; c < C; ++c) {
+        const int64_t T = sc[c].steps + 1;
+        for (size_t u = 0; u < n; ++u) {
+            const int64_t lab = r->labels[a[c * r->npad + u]];
+            const int64_t t_r = last_flipped[c * n + u];
+            // k = 2 (fc_flip2.hip): every run of u added (L0 + L1 - 2 a_r) per yield; the last
+            // run's share is -a_R t_R instead
+            if (r->p.k == 2 && t_r != 0) part_sum[c * n + u] += (lab - lsum) * t_r;
+            if (t_r == 0) part_sum[c * n + u] = T * lab;  // grid_chain_sec11.py:416-418
+        }
+    }
+    return FC_OK;
+}
+
+int fc_run_read_flips_exact(fc_run *r, int64_t *flip_count, int64_t *occupancy, int64_t *last_accept) {
+    if (!r || !flip_count || !occupancy || !last_accept) return fail(FC_ERR_ARG, "fc_run_read_flips_exact: null argument");
+    if (!r->d_flip_count) return fail(FC_ERR_ARG, "fc_run_read_flips_exact: FC_DIAG_FLIPS_EXACT not enabled");
+    const size_t n = r->g.n, C = r->n_chains;
+    std::vector<int8_t> a(C * r->npad);
+    std::vector<fc::ChainScalars> sc;
+    if (int rc = download_scalars(r, 0, r->n_chains, sc)) return rc;
+    HIP_TRY(hipMemcpy(flip_count, r->d_flip_count, C * n * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(occupancy, r->d_occ_acc, C * n * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(last_accept, r->d_last_accept, C * n * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(a.data(), r->d_assign, a.size(), hipMemcpyDeviceToHost));
+    for (size_t c = 0; c < C; ++c) {
+        // sum_t L(a_t) = L(a_0) s_1 + L(a_1)(s_2 - s_1) + ... = L(a_now) T - sum_flips (L_new - L_old) s
+        const int64_t T = sc[c].steps + 1;
+        for (size_t u = 0; u < n; ++u) occupancy[c * n + u] += (int64_t)r->labels[a[c * r->npad + u]] * T;
+    }
+    return FC_OK;
+}
+
+int fc_run_read_wait_expected(fc_run *r, double *out) {
+    if (!r || !out) return fail(FC_ERR_ARG, "fc_run_read_wait_expected: null argument");
+    if (!r->d_nb_hist) return fail(FC_ERR_ARG, "fc_run_read_wait_expected: FC_DIAG_HIST not enabled");
+    if (int rc = fc_run_sync(r)) return rc;
+    const size_t n = r->g.n, C = r->n_chains, W = (size_t)r->nb_w;
+    std::vector<int64_t> h(C * W);
+    HIP_TRY(hipMemcpy(h.data(), r->d_nb_hist, h.size() * 8, hipMemcpyDeviceToHost));
+    // geom_wait (:147-148): np.random.geometric(p) - 1 with p = |B| / (N^k - 1): mean 1/p - 1
+    const double M = std::pow((double)n, (double)r->p.k) - 1.0;
+    for (size_t c = 0; c < C; ++c) {
+        double s = 0.0;
+        for (size_t b = 1; b < W; ++b)
+            if (h[c * W + b]) s += (double)h[c * W + b] * (M / (double)b - 1.0);
+        out[c] = s;
+    }
+    return FC_OK;
+}
+
+}  // extern "C"

@@ -7,13 +7,19 @@
 // int32 pop[n], int32 has_pos, double pos[2 n] (if has_pos), uint32 flags, int32 k,
 // int32 n_steps, int8 assign[n] (if n_steps > 0).  The header sizes are taken as given, so a
 // malformed file must be rejected by the builder's checks, not by the harness.
+// Optional tail, for the run planner (csrc/fc_plan.cpp, the host half of fc_run_create): int32
+// n_chains, int32 pop_lo, int32 pop_hi, int32 tune_nsub, then int8 assign[n] if n_steps == 0.
+// With an assignment at hand (n_steps > 0 or the tail) the planner runs after GRAPH on k and
+// that assignment for every chain (no tail: 1 chain, bounds [0, INT32_MAX], tune_nsub 0) and
+// prints its code and message, chain_lds_bytes, dgraph and each chain's initial cut and nb.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <string>
 #include <vector>
 
-#include "../../flipcomplexityempirical_amd/csrc/fc_internal.h"
+#include "../../flipcomplexityempirical_amd/csrc/fc_plan.h"
 #include "../../oracle/flipref.h"
 
 template <typename T>
@@ -40,6 +46,9 @@ int main(int argc, char **argv) {
     if (!rd(f, &flags, 1) || !rd(f, &k, 1) || !rd(f, &n_steps, 1)) return 2;
     std::vector<int8_t> assign((size_t)n);
     if (n_steps > 0 && !rd(f, assign.data(), assign.size())) return 2;
+    int32_t tail[4] = {1, 0, INT32_MAX, 0};  // n_chains, pop_lo, pop_hi, tune_nsub
+    const bool has_tail = std::fread(tail, sizeof(int32_t), 4, f) == 4;
+    if (has_tail && n_steps <= 0 && !rd(f, assign.data(), assign.size())) return 2;
     std::fclose(f);
     // the builder reads row_ptr[n] entries of col_idx: hand it a buffer of exactly nnz
     // entries, so that a row_ptr claiming more is an ASan-visible overread unless rejected
@@ -58,6 +67,34 @@ int main(int argc, char **argv) {
     for (int32_t v = 0; v < g.n; ++v) exact += (g.meta[v] >> 8) & 1u;
     std::printf("GRAPH n=%d E=%d ring_max=%d exact=%lld gamma=%d planar=%d\n", g.n, g.n_edges, g.ring_max,
                 (long long)exact, g.n_gamma, (int)g.planar);
+    if ((n_steps > 0 || has_tail) && tail[0] > 0) {
+        // buffers of exactly the sizes the planner may read: an index past them is ASan-visible
+        const int32_t n_chains = tail[0];
+        std::vector<int8_t> init((size_t)n_chains * (size_t)n);
+        for (int32_t c = 0; c < n_chains; ++c) std::memcpy(init.data() + (size_t)c * n, assign.data(), (size_t)n);
+        fc_params p;
+        std::memset(&p, 0, sizeof p);
+        p.struct_size = (uint32_t)sizeof(fc_params);
+        p.abi_version = FC_ABI_VERSION;
+        p.k = k;
+        p.base = 1.5;
+        p.pop_lo = tail[1];
+        p.pop_hi = tail[2];
+        p.hit_lo = 1;
+        p.hit_hi = 0;
+        p.seed = 12345;
+        p.proposal = k == 2 ? FC_PROPOSE_BI_SIGN : FC_PROPOSE_PAIR;
+        p.diag_mask = FC_DIAG_WAIT | FC_DIAG_HIST | FC_DIAG_FLIPS;
+        p.tune_nsub = tail[3];
+        fc::RunPlan plan;
+        std::string msg;
+        const int rc = fc::plan_run(g, p, n_chains, init.data(), nullptr, plan, msg);
+        std::printf("PLAN rc=%d msg=%s\n", rc, msg.c_str());
+        if (rc == FC_OK) {
+            std::printf("PLAN_OK chain_lds_bytes=%d dgraph=%d\n", plan.chain_lds_bytes, (int)plan.dgraph);
+            for (int32_t c = 0; c < n_chains; ++c) std::printf("CHAIN %d cut=%d nb=%d\n", c, plan.sc[c].cut, plan.sc[c].nb);
+        }
+    }
     if (n_steps <= 0) return 0;
     // the oracle on the same CSR: every output buffer and the trace on
     std::vector<int32_t> labels(k);

@@ -6,6 +6,7 @@ lattices, the Delaunay workload and malformed CSR / position inputs.  Any saniti
 aborts the harness (``-fno-sanitize-recover=all``), so a clean exit with the expected verdict
 is the pass condition.  CPU only."""
 import fcntl
+import functools
 import os
 import shutil
 import subprocess
@@ -35,7 +36,8 @@ def harness():
     return EXE
 
 
-def _write(path, n, row, col, pop, pos=None, flags=0, k=2, n_steps=0, assign=None, nnz=None):
+def _write(path, n, row, col, pop, pos=None, flags=0, k=2, n_steps=0, assign=None, nnz=None, plan=None):
+    """``plan``: the optional tail for the run planner, (n_chains, pop_lo, pop_hi, tune_nsub)."""
     row = np.asarray(row, dtype=np.int32)
     col = np.asarray(col, dtype=np.int32)
     with open(path, "wb") as f:
@@ -50,6 +52,10 @@ def _write(path, n, row, col, pop, pos=None, flags=0, k=2, n_steps=0, assign=Non
         np.asarray([k, n_steps], dtype=np.int32).tofile(f)
         if n_steps > 0:
             np.asarray(assign, dtype=np.int8).tofile(f)
+        if plan is not None:
+            np.asarray(plan, dtype=np.int32).tofile(f)
+            if n_steps <= 0:
+                np.asarray(assign, dtype=np.int8).tofile(f)
 
 
 def _run(exe, path):
@@ -67,6 +73,7 @@ def _spec_case(spec, k, plan, steps):
                 pos=None if spec.pos is None else spec.pos, k=k, n_steps=steps, assign=a)
 
 
+@functools.lru_cache(maxsize=None)
 def _lattices():
     sec11, frank = G.sec11_graph(), G.frank_graph()
     tri = G.triangular_graph(30, 58)
@@ -90,6 +97,70 @@ def test_sanitized_graph_and_oracle_on_workloads(harness, tmp_path, name):
     p2 = str(tmp_path / f"{name}_nopos.bin")
     _write(p2, c["n"], c["row"], c["col"], c["pop"], pos=None, flags=1)
     assert "GRAPH" in _run(harness, p2)
+
+
+def _plan_lines(out):
+    """(rc, message, {key: int} of PLAN_OK, [(cut, nb)] per chain) from the harness output."""
+    head = [ln for ln in out.splitlines() if ln.startswith("PLAN rc=")]
+    assert len(head) == 1, out
+    rc, _, msg = head[0][len("PLAN rc="):].partition(" msg=")
+    ok = [dict(kv.split("=") for kv in ln.split()[1:]) for ln in out.splitlines() if ln.startswith("PLAN_OK")]
+    chains = [tuple(int(kv.split("=")[1]) for kv in ln.split()[2:]) for ln in out.splitlines() if ln.startswith("CHAIN ")]
+    return int(rc), msg, ({k: int(v) for k, v in ok[0].items()} if ok else {}), chains
+
+
+@pytest.mark.parametrize("name", ["sec11", "frank", "triangular_k4", "delaunay_k6"])
+def test_sanitized_planner_on_workloads(harness, tmp_path, name):
+    """The host half of fc_run_create (csrc/fc_plan.cpp) under ASan + UBSan: each chain's initial
+    |cut| and |B| equal the counts taken from the CSR and the assignment in numpy."""
+    c = _lattices()[name]
+    p = str(tmp_path / f"{name}_plan.bin")
+    _write(p, c["n"], c["row"], c["col"], c["pop"], pos=c["pos"], k=c["k"], assign=c["assign"],
+           plan=(3, 0, 2**31 - 1, 0))
+    rc, msg, ok, chains = _plan_lines(_run(harness, p))
+    assert rc == 0, msg
+    a = np.asarray(c["assign"])
+    row, col = np.asarray(c["row"]), np.asarray(c["col"])
+    u = np.repeat(np.arange(c["n"]), np.diff(row))
+    foreign = a[u] != a[col]
+    cut, nb = int(foreign.sum()) // 2, int(np.unique(u[foreign]).size)
+    assert cut > 0 and chains == [(cut, nb)] * 3, (cut, nb, chains)
+    if name == "sec11":
+        # the k = 2 LDS layout's size as the comment at its computation (fc_plan.cpp plan_lds)
+        # states it: 4 * 1600 + 18 * 8 + 24 * 25 + 1280 + 16 + 64 * 24 + 40.  (The comment said
+        # 10,032 B before the planner was split out; the code gave 10,016 then as now.)
+        assert ok["chain_lds_bytes"] == 10016, ok
+
+
+def _grid_plan_cases():
+    g = G.grid_graph(4, 4)
+    halves = (np.asarray(g.pos)[:, 0] > np.median(np.asarray(g.pos)[:, 0])).astype(np.int8)
+    checker = (np.rint(np.asarray(g.pos)).astype(int).sum(axis=1) % 2).astype(np.int8)
+    bad_id = halves.copy()
+    bad_id[5] = 2
+    total = int(np.asarray(g.pop).sum())
+    # name: (k, assign, (n_chains, pop_lo, pop_hi, tune_nsub), code, word in the message)
+    return g, {
+        "valid": (2, halves, (2, 0, 2**31 - 1, 0), 0, ""),
+        "district_id_k": (2, bad_id, (2, 0, 2**31 - 1, 0), -1, "district id"),
+        "checkerboard": (2, checker, (2, 0, 2**31 - 1, 0), -2, "contiguity"),
+        "pop_bounds": (2, halves, (2, total // 2 + 1, total, 0), -2, "population"),
+        "k33": (33, halves, (2, 0, 2**31 - 1, 0), -4, "k must be"),
+        "tune_nsub3": (2, halves, (2, 0, 2**31 - 1, 3), -1, "tune_nsub"),
+    }
+
+
+@pytest.mark.parametrize("name", ["valid", "district_id_k", "checkerboard", "pop_bounds", "k33", "tune_nsub3"])
+def test_sanitized_planner_refusals(harness, tmp_path, name):
+    """fc_run_create's refusals, reached without a GPU: FC_ERR_ARG (-1), FC_ERR_INVALID_STATE
+    (-2) and FC_ERR_UNSUPPORTED (-4) with their messages, on the 4x4 grid."""
+    g, cases = _grid_plan_cases()
+    k, assign, plan, code, word = cases[name]
+    p = str(tmp_path / f"plan_{name}.bin")
+    _write(p, g.n, g.row_ptr, g.col_idx, g.pop, pos=g.pos, k=k, assign=assign, plan=plan)
+    rc, msg, ok, chains = _plan_lines(_run(harness, p))
+    assert rc == code and word in msg, (rc, msg)
+    assert (len(chains) == plan[0]) == (code == 0)
 
 
 def test_sanitized_delaunay_10k(harness, tmp_path):

@@ -10,12 +10,19 @@ CS=$R/flipcomplexityempirical_amd/csrc
 OBJ=/tmp/fc_varobj; mkdir -p "$OBJ" "$R/abl"
 VFILE=${VFILE:-fc_flip2.hip}
 F="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -DFC_VARIANT_BUILD"
+# the product's source list (build.py SOURCES; HOST_ONLY: plain C++, compiled without the offload flags)
+list() { python3 -c "import runpy; print(' '.join(runpy.run_path('$R/flipcomplexityempirical_amd/build.py')['$1']))"; }
+SOURCES=$(list SOURCES)
+HOST_ONLY=" $(list HOST_ONLY) "
 pids=()
-for s in fc_flip2.hip fc_deal.hip fc_kernels.hip fc_series.hip fc_recom.hip fc_capi.cpp fc_graph.cpp; do
+for s in $SOURCES; do
   [ "$s" = "$VFILE" ] && continue
   o=$OBJ/${s%.*}.o
   if [ ! -f "$o" ] || [ "$CS/$s" -nt "$o" ] || [ -n "$(find $CS -name '*.h' -newer $o)" ]; then
-    eval /opt/rocm/bin/hipcc $F -c -o "$o" "$CS/$s" & pids+=($!)
+    case "$HOST_ONLY" in
+      *" $s "*) eval /opt/rocm/bin/hipcc -x c++ ${F#--offload-arch=gfx950} -c -o "$o" "$CS/$s" & pids+=($!) ;;
+      *) eval /opt/rocm/bin/hipcc $F -c -o "$o" "$CS/$s" & pids+=($!) ;;
+    esac
   fi
 done
 # PATCH=<file>: the variants compile a patched copy of VFILE (tools/patches/; timing-only code
@@ -35,7 +42,7 @@ done
 for p in "${pids[@]}"; do wait $p; done
 for n in "${names[@]}"; do
   objs=""
-  for s in fc_flip2.hip fc_deal.hip fc_kernels.hip fc_series.hip fc_recom.hip fc_capi.cpp fc_graph.cpp; do
+  for s in $SOURCES; do
     if [ "$s" = "$VFILE" ]; then objs="$objs $OBJ/v_$n.o"; else objs="$objs $OBJ/${s%.*}.o"; fi
   done
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -fPIC -shared -o "$R/abl/$n.so" $objs
