@@ -30,6 +30,7 @@ FC_FLAG_FORCE_BFS = 0x1
 FC_FLAG_SERIES_TWO_PASS = 0x2  # fc_run_frame_series_changes' two-pass form (cross-check)
 FC_FLAG_TALLY_LOG_SMALL = 0x4  # a 64-entry tally log: the overflow path's atomics (cross-check)
 FC_FLAG_NB_PAIRS = 0x8  # k > 2: |b_nodes| counts the pair updater's (node, district) pairs (:151-153)
+FC_FLAG_VOTES_GLOBAL_CUR = 0x10  # fc_run_election_series: current assignment in a global row (cross-check)
 FC_ACCEPT_CUT, FC_ACCEPT_UNIFORM, FC_ACCEPT_ANNEAL = 0, 1, 2
 FC_LADDER_HIST = 0x1  # fc_run_set_ladders: per-rung |cut| / |B| histograms
 FC_CON_CONTIG, FC_CON_POP, FC_CON_BOUNDARY, FC_CON_FIXED, FC_CON_EMPTY = 0x1, 0x2, 0x4, 0x8, 0x100
@@ -45,6 +46,7 @@ EXPORTED = [
     "fc_run_kernel_name", "fc_run_n_chains", "fc_run_chain_lds_bytes", "fc_run_nb_width", "fc_run_diag_paths",
     "fc_run_set_ladders", "fc_run_exchange", "fc_run_read_rungs", "fc_run_read_bases", "fc_run_read_rung_stats",
     "fc_ladder_swap_threshold",
+    "fc_run_set_elections", "fc_run_election_series", "fc_election_eval",
     "fc_run_destroy",
     "fc_device_count", "fc_device_pci_id", "fc_last_error", "fc_build_flags", "fc_build_id",
 ]
@@ -235,6 +237,9 @@ def load(build_if_missing: bool = True, allow_variant: bool = False):
     L.fc_run_read_bases.argtypes = [vp, _P(dbl)]
     L.fc_run_read_rung_stats.argtypes = [vp, _P(RungStats), _P(i64), _P(i64)]
     L.fc_ladder_swap_threshold.argtypes = [dbl, dbl, i32, _P(ctypes.c_uint64)]
+    L.fc_run_set_elections.argtypes = [vp, i32, _P(i32), i32, _P(i32), _P(i32), i32, _P(i64)]
+    L.fc_run_election_series.argtypes = [vp, i32, i32, _P(i64), _P(i64), _P(i64), _P(i64), _P(i64), _P(i64)]
+    L.fc_election_eval.argtypes = [i32, _P(i64), _P(i64), _P(i32), _P(i64)]
     L.fc_device_pci_id.argtypes = [i32, ctypes.c_char_p, i32]
     L.fc_run_destroy.argtypes = [vp]
     L.fc_run_destroy.restype = None

@@ -39,7 +39,7 @@ from typing import Any, Callable, Dict, Hashable, Iterable, List, Optional, Sequ
 import numpy as np
 
 from . import _lib
-from .graphs import GraphSpec, from_networkx, log1mp_table, slope_frame
+from .graphs import GraphSpec, from_networkx, log1mp_table, node_columns, slope_frame
 
 # ----------------------------------------------------------------------------------------
 # gerrychain updaters / constraints restated for host-side use  [gc-0.2]
@@ -59,6 +59,73 @@ class Tally:
         for nd, p in partition.assignment.items():
             out[p] = out.get(p, 0) + sum(g.nodes[nd][f] for f in self.fields)
         return out
+
+
+class ElectionResults:
+    """What an :class:`Election` updater returns for one partition: per-party, per-part vote
+    totals and the scores read off them (``gerrychain.updaters.ElectionResults`` [gc-0.2], two
+    parties).  A part is won by the party with strictly more votes; a tie is won by neither."""
+
+    def __init__(self, election: "Election", totals_for_party: Dict[Any, Dict[Any, int]]):
+        self.election = election
+        self.totals_for_party = totals_for_party
+        self.parts = list(next(iter(totals_for_party.values())).keys())
+
+    def _other(self, party):
+        a, b = self.election.parties
+        if party not in (a, b):
+            raise KeyError(party)
+        return b if party == a else a
+
+    def totals(self, part) -> int:
+        return sum(t[part] for t in self.totals_for_party.values())
+
+    def won(self, party, part) -> bool:
+        return self.totals_for_party[party][part] > self.totals_for_party[self._other(party)][part]
+
+    def seats(self, party) -> int:
+        return sum(self.won(party, part) for part in self.parts)
+
+    wins = seats
+
+    def efficiency_gap(self) -> float:
+        """(wasted votes of the second party - wasted votes of the first) / total votes: positive
+        when it favours the first party (``gerrychain.metrics.efficiency_gap``; a tied part, which
+        neither party wins, adds nothing, as in the device's ``gap_sum`` -- DESIGN.md §5c)."""
+        a, b = self.election.parties
+        wasted_a = wasted_b = total = 0.0
+        for part in self.parts:
+            va, vb = self.totals_for_party[a][part], self.totals_for_party[b][part]
+            total += va + vb
+            if va > vb:
+                wasted_a += va - (va + vb) / 2
+                wasted_b += vb
+            elif vb > va:
+                wasted_a += va
+                wasted_b += vb - (va + vb) / 2
+        return (wasted_b - wasted_a) / total if total else 0.0
+
+
+class Election:
+    """``gerrychain.updaters.Election`` [gc-0.2] for two parties: ``Election(name, {party_a:
+    column, party_b: column})``, the columns being integer node attributes.  Called on a
+    partition it returns :class:`ElectionResults`.  As an updater of a chain's initial state it
+    makes :meth:`MarkovChain.run` replay the election over every yield on the device
+    (``ChainResult.elections``).  More than two parties raise ``NotImplementedError``."""
+
+    def __init__(self, name: str, parties_to_columns: Dict[Any, str], alias: Optional[str] = None):
+        if len(parties_to_columns) != 2:
+            raise NotImplementedError("Election: two parties only")
+        self.name = name
+        self.alias = alias or name
+        self.parties = list(parties_to_columns.keys())
+        self.columns = [parties_to_columns[p] for p in self.parties]
+        if self.columns[0] == self.columns[1]:
+            raise ValueError("Election: the two parties need different columns")
+        self.parties_to_columns = dict(parties_to_columns)
+
+    def __call__(self, partition) -> ElectionResults:
+        return ElectionResults(self, {party: Tally(col)(partition) for party, col in self.parties_to_columns.items()})
 
 
 def cut_edges(partition):
@@ -731,14 +798,37 @@ class MarkovChain:
                     _name(self.initial_state.updaters.get("slope")) == "boundary_slope":
                 neg = any(isinstance(nd, tuple) and nd[1] < 0 for nd in self.cspec.spec.nodes)
                 frame = "frank" if neg else "sec11"
-        if series:
+        # Election updaters of the initial state: replayed over every yield on the device from the
+        # flip log, so they need the event log whether or not the per-yield lists are kept
+        elections = {key: u for key, u in self.initial_state.updaters.items() if isinstance(u, Election)}
+        log = series or bool(elections)
+        if log:
             diag |= _lib.FC_DIAG_SERIES
         if corrected:
             diag |= _lib.FC_DIAG_FLIPS_EXACT
-        run = self._make_run(trace=False, diag=diag, event_cap=max(self.total_steps, 1) if series else 0)
+        run = self._make_run(trace=False, diag=diag, event_cap=max(self.total_steps, 1) if log else 0)
+        col_names: List[str] = []
+        if elections:
+            for u in elections.values():
+                col_names += [c for c in u.columns if c not in col_names]
+            cols = node_columns(self.initial_state.graph, self.cspec.spec.nodes, col_names)
+            run.set_elections(np.stack([cols[c] for c in col_names], axis=1),
+                              [(col_names.index(u.columns[0]), col_names.index(u.columns[1]))
+                               for u in elections.values()])
         if self.total_steps > 1:
             run.steps(self.total_steps - 1)
         res = ChainResult.from_run(self, run, 0)
+        if elections:
+            es = run.election_series(0, 1)
+            res.elections = {}
+            for e, (key, u) in enumerate(elections.items()):
+                ja, jb = col_names.index(u.columns[0]), col_names.index(u.columns[1])
+                res.elections[key] = {"parties": list(u.parties), "columns": list(u.columns),
+                                      "yields": int(es["yields"][0]),
+                                      "seats_hist": es["seats_hist"][0, e].copy(),
+                                      "wins_sum": es["wins_sum"][0, e].copy(),
+                                      "gap_sum": int(es["gap_sum"][0, e]),
+                                      "tally_sum": es["tally_sum"][0][:, [ja, jb]].copy()}
         if corrected:
             sp = self.cspec.spec
             xf, xo, xl = run.flips_exact()
@@ -797,6 +887,10 @@ class ChainResult:
     occupancy: Optional[Dict[Hashable, int]] = None    # sum_t label (part_sum lacks final segments)
     last_accept: Optional[Dict[Hashable, int]] = None  # yield of the last accepted flip
     waits_expected: Optional[float] = None             # sum_t E[geom | |B_t|] (cached-sample-free)
+    # per Election updater of the initial state (by updater key), over all yields:
+    # seats_hist [k + 1], wins_sum [k] (parts in label order), gap_sum, tally_sum [k, 2] (the two
+    # parties' columns), parties, columns, yields
+    elections: Optional[Dict[str, Dict[str, Any]]] = None
 
     def heatmaps(self, shape=(40, 40), offset=(0, 0)) -> Dict[str, np.ndarray]:
         """The driver's ``A2`` arrays (``grid_chain_sec11.py:431-528``): ``A2[n[0], n[1]]``

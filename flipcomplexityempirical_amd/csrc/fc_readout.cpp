@@ -445,6 +445,152 @@ int fc_run_frame_series_changes(fc_run *r, int32_t c0, int32_t nc, int32_t n_fra
     return FC_OK;
 }
 
+// ---- election series (fc_votes.h, fc_votes.hip) -------------------------------
+
+int fc_election_eval(int32_t k, const int64_t *a, const int64_t *b, int32_t *seats, int64_t *gap) {
+    if (!a || !b) return fail(FC_ERR_ARG, "fc_election_eval: null argument");
+    if (k < 1 || k > fc::kMaxKGeneral) return fail(FC_ERR_ARG, "fc_election_eval: k must be 1..32");
+    int32_t s = 0;
+    int64_t gsum = 0;
+    for (int32_t d = 0; d < k; ++d) {
+        if (a[d] < 0 || b[d] < 0 || a[d] > INT32_MAX || b[d] > INT32_MAX)
+            return fail(FC_ERR_ARG, "fc_election_eval: tallies must be in 0 .. 2^31 - 1");
+        int32_t w;
+        int64_t g;
+        fc::election_rule(a[d], b[d], w, g);
+        s += w;
+        gsum += g;
+    }
+    if (seats) *seats = s;
+    if (gap) *gap = gsum;
+    return FC_OK;
+}
+
+int fc_run_set_elections(fc_run *r, int32_t n_cols, const int32_t *node_cols, int32_t n_elections,
+                         const int32_t *col_a, const int32_t *col_b, int32_t n_gap_edges, const int64_t *gap_edges) {
+    if (!r || !node_cols) return fail(FC_ERR_ARG, "fc_run_set_elections: null argument");
+    if (r->p.proposal == FC_PROPOSE_RECOM)
+        return fail(FC_ERR_UNSUPPORTED, "fc_run_set_elections: the election series replays the flip log (not ReCom)");
+    if (!r->d_events) return fail(FC_ERR_ARG, "fc_run_set_elections: FC_DIAG_SERIES not enabled");
+    if (n_cols < 1 || n_cols > fc::kVoteMaxCols) return fail(FC_ERR_ARG, "fc_run_set_elections: n_cols must be 1..8");
+    if (n_elections < 0 || n_elections > fc::kVoteMaxElections)
+        return fail(FC_ERR_ARG, "fc_run_set_elections: n_elections must be 0..4");
+    if (n_elections > 0 && (!col_a || !col_b)) return fail(FC_ERR_ARG, "fc_run_set_elections: null election columns");
+    if (n_gap_edges < 0 || n_gap_edges > fc::kVoteMaxEdges)
+        return fail(FC_ERR_ARG, "fc_run_set_elections: n_gap_edges must be 0..256");
+    if (n_gap_edges > 0 && !gap_edges) return fail(FC_ERR_ARG, "fc_run_set_elections: null gap_edges");
+    const int32_t n = r->g.n;
+    for (int32_t j = 0; j < n_cols; ++j) {
+        int64_t tot = 0;
+        for (int32_t u = 0; u < n; ++u) {
+            const int32_t x = node_cols[(size_t)u * n_cols + j];
+            if (x < 0)
+                return fail(FC_ERR_ARG, "fc_run_set_elections: negative value in column " + std::to_string(j));
+            tot += x;
+        }
+        if (tot > INT32_MAX)
+            return fail(FC_ERR_ARG, "fc_run_set_elections: column " + std::to_string(j) + " totals over 2^31 - 1");
+    }
+    for (int32_t e = 0; e < n_elections; ++e)
+        if (col_a[e] < 0 || col_a[e] >= n_cols || col_b[e] < 0 || col_b[e] >= n_cols || col_a[e] == col_b[e])
+            return fail(FC_ERR_ARG, "fc_run_set_elections: election " + std::to_string(e) +
+                                        " needs two different columns below n_cols");
+    for (int32_t i = 1; i < n_gap_edges; ++i)
+        if (gap_edges[i] <= gap_edges[i - 1])
+            return fail(FC_ERR_ARG, "fc_run_set_elections: gap_edges must be strictly ascending");
+    // rows padded to the kernel instance's column count
+    const int32_t ncp = fc::votes_padded_cols(n_cols);
+    std::vector<int32_t> cols((size_t)n * ncp, 0);
+    for (int32_t u = 0; u < n; ++u)
+        std::copy(node_cols + (size_t)u * n_cols, node_cols + (size_t)(u + 1) * n_cols, cols.begin() + (size_t)u * ncp);
+    if (int rc = fc_run_sync(r)) return rc;  // a reader of the previous tables may still run
+    r->el_n_cols = 0;
+    if (int rc = r->d_el_cols.upload(cols)) return rc;
+    if (int rc = r->d_el_edges.upload(gap_edges, (size_t)n_gap_edges)) return rc;
+    for (int32_t e = 0; e < fc::kVoteMaxElections; ++e) {
+        r->el_col_a[e] = e < n_elections ? col_a[e] : 0;
+        r->el_col_b[e] = e < n_elections ? col_b[e] : 0;
+    }
+    r->el_n_el = n_elections;
+    r->el_n_edges = n_gap_edges;
+    r->el_n_cols = n_cols;
+    return FC_OK;
+}
+
+int fc_run_election_series(fc_run *r, int32_t c0, int32_t nc, int64_t *tally_now, int64_t *tally_sum,
+                           int64_t *seats_hist, int64_t *wins_sum, int64_t *gap_sum, int64_t *gap_hist) {
+    if (!r) return fail(FC_ERR_ARG, "fc_run_election_series: null run");
+    if (r->p.proposal == FC_PROPOSE_RECOM)
+        return fail(FC_ERR_UNSUPPORTED, "fc_run_election_series: the election series replays the flip log (not ReCom)");
+    if (!r->d_events) return fail(FC_ERR_ARG, "fc_run_election_series: FC_DIAG_SERIES not enabled");
+    if (r->el_n_cols == 0) return fail(FC_ERR_ARG, "fc_run_election_series: call fc_run_set_elections first");
+    if (c0 < 0 || nc < 0 || c0 + nc > r->n_chains) return fail(FC_ERR_ARG, "fc_run_election_series: chain range");
+    if (gap_hist && r->el_n_edges == 0)
+        return fail(FC_ERR_ARG, "fc_run_election_series: gap_hist needs gap_edges (fc_run_set_elections)");
+    if (nc == 0) return FC_OK;
+    std::vector<fc::ChainScalars> sc;
+    if (int rc = download_scalars(r, c0, nc, sc)) return rc;
+    std::vector<int64_t> meta((size_t)3 * nc);
+    for (int32_t i = 0; i < nc; ++i) {
+        if (int rc = check_event_overflow(r, "fc_run_election_series", c0 + i, sc[i])) return rc;
+        if (sc[i].steps - sc[i].ser_t0 + 1 >= (int64_t(1) << 30))
+            return fail(FC_ERR_ARG, "fc_run_election_series: chain " + std::to_string(c0 + i) +
+                                        "'s window has 2^30 yields or more; reset the series window more often");
+        meta[i] = sc[i].ev_len;
+        meta[(size_t)nc + i] = sc[i].ser_t0;
+        meta[(size_t)2 * nc + i] = sc[i].steps + 1;
+    }
+    const int32_t k = r->p.k, n_cols = r->el_n_cols, n_el = r->el_n_el, n_edges = r->el_n_edges;
+    // the outputs, one after the other in one device buffer
+    const size_t sz[6] = {(size_t)nc * k * n_cols, (size_t)nc * k * n_cols, (size_t)nc * n_el * (k + 1),
+                          (size_t)nc * n_el * k,   (size_t)nc * n_el,       (size_t)nc * n_el * (n_edges + 1)};
+    size_t off[7] = {0};
+    for (int i = 0; i < 6; ++i) off[i + 1] = off[i] + sz[i];
+    int q;
+    if ((q = r->d_el_meta.grow(meta.size()))) return q;
+    if ((q = r->d_el_out.grow(off[6]))) return q;
+    const bool global_cur = (r->p.flags & FC_FLAG_VOTES_GLOBAL_CUR) || !fc::votes_cur_in_lds(r->npad, k, n_edges);
+    if (global_cur && (q = r->d_el_cur.grow((size_t)nc * r->npad))) return q;
+    HIP_TRY(hipMemcpyAsync(r->d_el_meta, meta.data(), meta.size() * 8, hipMemcpyHostToDevice, r->stream));
+    fc::VotesParams vp{};
+    vp.a0 = r->d_ser_a0;
+    vp.npad = r->npad;
+    vp.n = r->g.n;
+    vp.k = k;
+    vp.events = r->d_events;
+    vp.ev_cap = r->ev_cap;
+    vp.ev_len = r->d_el_meta;
+    vp.t0 = r->d_el_meta + nc;
+    vp.t_end = r->d_el_meta + 2 * (size_t)nc;
+    vp.c0 = c0;
+    vp.nc = nc;
+    vp.cols = r->d_el_cols;
+    vp.n_cols = n_cols;
+    vp.n_el = n_el;
+    for (int e = 0; e < fc::kVoteMaxElections; ++e) {
+        vp.col_a[e] = r->el_col_a[e];
+        vp.col_b[e] = r->el_col_b[e];
+    }
+    vp.n_edges = n_edges;
+    vp.edges = r->d_el_edges;
+    vp.cur = global_cur ? r->d_el_cur.get() : nullptr;
+    int64_t *const d_out = r->d_el_out;
+    vp.tally_now = d_out + off[0];
+    vp.tally_sum = d_out + off[1];
+    vp.seats_hist = d_out + off[2];
+    vp.wins_sum = d_out + off[3];
+    vp.gap_sum = d_out + off[4];
+    vp.gap_hist = d_out + off[5];
+    const int e = fc::launch_votes(vp, global_cur, r->stream);
+    if (e) return fail(FC_ERR_HIP, std::string("election series: ") + hipGetErrorString((hipError_t)e));
+    int64_t *const host[6] = {tally_now, tally_sum, seats_hist, wins_sum, gap_sum, gap_hist};
+    for (int i = 0; i < 6; ++i)
+        if (host[i] && sz[i])
+            HIP_TRY(hipMemcpyAsync(host[i], d_out + off[i], sz[i] * 8, hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    return FC_OK;
+}
+
 int fc_run_read_hist(fc_run *r, int64_t *cut_hist, int64_t *nb_hist) {
     if (!r || !cut_hist || !nb_hist) return fail(FC_ERR_ARG, "fc_run_read_hist: null argument");
     if (!r->d_cut_hist) return fail(FC_ERR_ARG, "fc_run_read_hist: FC_DIAG_HIST not enabled");

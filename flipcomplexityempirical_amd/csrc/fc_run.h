@@ -11,6 +11,7 @@
 #include "fc_internal.h"
 #include "fc_ladder.h"
 #include "fc_plan.h"
+#include "fc_votes.h"
 
 namespace fc {
 
@@ -150,6 +151,14 @@ struct fc_run : fc::RunShape {
     DevBuf<int64_t> d_fc_len, d_fc_t0, d_fc_cnt, d_fc_off;
     DevBuf<int64_t> d_fc_t;
     DevBuf<double> d_fc_sa;     // [2 * change points the outputs hold]
+    // election series (fc_run_set_elections; fc_votes.h, fc_votes.hip).  el_n_cols 0: not set
+    int32_t el_n_cols = 0, el_n_el = 0, el_n_edges = 0;
+    int32_t el_col_a[fc::kVoteMaxElections] = {0}, el_col_b[fc::kVoteMaxElections] = {0};
+    DevBuf<int32_t> d_el_cols;    // [n * votes_padded_cols(el_n_cols)]
+    DevBuf<int64_t> d_el_edges;   // [el_n_edges]
+    DevBuf<int64_t> d_el_meta;    // per call: ev_len, t0, t_end of the chains read, [nc] each
+    DevBuf<int64_t> d_el_out;     // per call: the six outputs, one after the other
+    DevBuf<int8_t> d_el_cur;      // per call: current-assignment rows when they are not kept in LDS
     char kname[96] = {0};       // last launched flip-kernel instance
     // replica exchange (fc_run_set_ladders; fc_ladder.h, fc_exchange.hip).  Slots are flat: ladder
     // l's rung r is slot lad_off[l] + r

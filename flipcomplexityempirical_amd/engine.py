@@ -535,6 +535,57 @@ class FlipRun:
         bounds = np.concatenate([[t0], ev["t"], [T + 1]]).astype(np.int64)
         return np.repeat(np.asarray(values)[:ev.size + 1], np.diff(bounds))
 
+    # ---- election series ----------------------------------------------
+    def set_elections(self, columns, elections: Sequence = (), gap_edges=None) -> "FlipRun":
+        """Attach node vote columns (``fc_run_set_elections``): ``columns`` is ``[n, n_cols]``
+        non-negative integers in canonical node order, ``elections`` a list of ``(col_a, col_b)``
+        column pairs (at most 4; none keeps the tallies only), ``gap_edges`` the strictly ascending
+        int64 bin edges of the efficiency-gap histogram in its doubled integer units (at most 256;
+        None: no histogram).  Callable again to replace them; a restored run needs it again."""
+        cols = np.asarray(columns)
+        if cols.ndim == 1:
+            cols = cols[:, None]
+        if cols.ndim != 2 or cols.shape[0] != self.graph.n:
+            raise ValueError("columns must be [n, n_cols]")
+        if not np.issubdtype(cols.dtype, np.integer):
+            raise ValueError("columns must be integers")
+        if cols.size and (cols.min() < -2 ** 31 or cols.max() > 2 ** 31 - 1):
+            raise ValueError("columns must hold int32 values")  # (the library checks the rest)
+        cols = np.ascontiguousarray(cols, dtype=np.int32)
+        el = np.ascontiguousarray(np.asarray(list(elections), dtype=np.int32).reshape(-1, 2))
+        ca, cb = np.ascontiguousarray(el[:, 0]), np.ascontiguousarray(el[:, 1])
+        edges = np.ascontiguousarray([] if gap_edges is None else gap_edges, dtype=np.int64).reshape(-1)
+        check(_lib.load().fc_run_set_elections(self.handle, int(cols.shape[1]), _p(cols, ctypes.c_int32),
+                                               int(el.shape[0]), _p(ca, ctypes.c_int32), _p(cb, ctypes.c_int32),
+                                               int(edges.size), _p(edges, ctypes.c_int64)), "fc_run_set_elections")
+        self._elections = (int(cols.shape[1]), int(el.shape[0]), int(edges.size))
+        return self
+
+    def election_series(self, c0: int = 0, nc: Optional[int] = None) -> Dict[str, np.ndarray]:
+        """Election statistics of chains ``c0 .. c0 + nc - 1`` over the series window, replayed
+        on the device from the flip log (``fc_run_election_series``; include/flipchain.h):
+        ``tally_now`` / ``tally_sum`` ``[nc, k, n_cols]``, ``seats_hist`` ``[nc, n_el, k + 1]``,
+        ``wins_sum`` ``[nc, n_el, k]``, ``gap_sum`` ``[nc, n_el]``, ``gap_hist``
+        ``[nc, n_el, n_edges + 1]`` (only with ``gap_edges``) and ``yields`` ``[nc]``, the yields of
+        each chain's window.  All int64."""
+        nc = self.n_chains - c0 if nc is None else int(nc)
+        n_cols, n_el, n_edges = getattr(self, "_elections", (1, 0, 0))
+        k = self.cfg.k
+        m = max(nc, 0)
+        out = {"tally_now": np.zeros((m, k, n_cols), dtype=np.int64),
+               "tally_sum": np.zeros((m, k, n_cols), dtype=np.int64),
+               "seats_hist": np.zeros((m, n_el, k + 1), dtype=np.int64),
+               "wins_sum": np.zeros((m, n_el, k), dtype=np.int64),
+               "gap_sum": np.zeros((m, n_el), dtype=np.int64)}
+        if n_edges:
+            out["gap_hist"] = np.zeros((m, n_el, n_edges + 1), dtype=np.int64)
+        check(_lib.load().fc_run_election_series(self.handle, int(c0), nc, *(
+            _p(out.get(key), ctypes.c_int64) for key in ("tally_now", "tally_sum", "seats_hist", "wins_sum",
+                                                         "gap_sum", "gap_hist"))), "fc_run_election_series")
+        st = self.stats()
+        out["yields"] = (st["steps"] - st["series_t0"] + 1)[c0:c0 + nc].astype(np.int64)
+        return out
+
     # ---- replica exchange (DESIGN.md "Replica exchange") ------------------------------
     def set_ladders(self, ladders: Sequence[Sequence[int]], hist: bool = False) -> "FlipRun":
         """``ladders``: lists of local chain indices, rung 0 first (``fc_run_set_ladders``; once

@@ -39,6 +39,8 @@ class GraphSpec:
     pos: Optional[np.ndarray] = None  # float64 [n, 2]
     nx_graph: object = None
     index: Dict[Hashable, int] = field(default_factory=dict)
+    # further integer node attributes carried along (vote columns: FlipRun.set_elections), each [n]
+    columns: Dict[str, np.ndarray] = field(default_factory=dict)
 
     @property
     def n(self) -> int:
@@ -70,8 +72,28 @@ class GraphSpec:
         return np.asarray([lut[assignment[nd]] for nd in self.nodes], dtype=np.int8)
 
 
-def from_networkx(g, pop_attr: str = "population", pos: Optional[Dict] = None) -> GraphSpec:
-    """Build a :class:`GraphSpec` from a networkx graph (nodes sorted for a canonical order)."""
+def node_columns(g, nodes: Sequence, names: Sequence[str]) -> Dict[str, np.ndarray]:
+    """The integer node attributes ``names`` of ``g`` as int64 arrays in the order of ``nodes``
+    (ValueError for a missing or non-integer value)."""
+    out = {}
+    for name in names:
+        vals = []
+        for nd in nodes:
+            if name not in g.nodes[nd]:
+                raise ValueError(f"node {nd!r} has no attribute {name!r}")
+            x = g.nodes[nd][name]
+            if isinstance(x, bool) or not isinstance(x, (int, np.integer)):
+                if not (isinstance(x, (float, np.floating)) and float(x).is_integer()):
+                    raise ValueError(f"node {nd!r}: attribute {name!r} = {x!r} is not an integer")
+            vals.append(int(x))
+        out[name] = np.asarray(vals, dtype=np.int64)
+    return out
+
+
+def from_networkx(g, pop_attr: str = "population", pos: Optional[Dict] = None,
+                  columns: Sequence[str] = ()) -> GraphSpec:
+    """Build a :class:`GraphSpec` from a networkx graph (nodes sorted for a canonical order).
+    ``columns``: names of integer node attributes to carry along (``GraphSpec.columns``)."""
     nodes = sorted(g.nodes())
     index = {nd: i for i, nd in enumerate(nodes)}
     n = len(nodes)
@@ -91,10 +113,11 @@ def from_networkx(g, pop_attr: str = "population", pos: Optional[Dict] = None) -
     if pos is not None:
         p = np.asarray([pos[nd] for nd in nodes], dtype=np.float64).reshape(n, 2)
     return GraphSpec(nodes=nodes, row_ptr=row_ptr, col_idx=col_idx, pop=popv, pos=p,
-                     nx_graph=g, index=index)
+                     nx_graph=g, index=index, columns=node_columns(g, nodes, columns))
 
 
-def from_json(src, pop_attr: str = "population", pos_attrs: Optional[Sequence[str]] = None) -> GraphSpec:
+def from_json(src, pop_attr: str = "population", pos_attrs: Optional[Sequence[str]] = None,
+              columns: Sequence[str] = ()) -> GraphSpec:
     """A gerrychain / networkx JSON graph -> :class:`GraphSpec`.
 
     ``src`` is a path, a file object or an already-parsed dict in networkx's
@@ -136,7 +159,7 @@ def from_json(src, pop_attr: str = "population", pos_attrs: Optional[Sequence[st
         pos = {nd: tuple(float(x) for x in g.nodes[nd]["pos"]) for nd in g.nodes}
     elif all(isinstance(nd, tuple) and len(nd) == 2 for nd in g.nodes):
         pos = {nd: (float(nd[0]), float(nd[1])) for nd in g.nodes}
-    return from_networkx(g, pop_attr=pop_attr, pos=pos)
+    return from_networkx(g, pop_attr=pop_attr, pos=pos, columns=columns)
 
 
 # --------------------------------------------------------------------------------------

@@ -100,6 +100,10 @@ extern "C" {
                                     (:155-156).  The histogram and log1mp then have
                                     fc_run_nb_width entries; no-op for k = 2.  Such runs commit
                                     one flip at a time (tune_multi_flip has no effect)           */
+#define FC_FLAG_VOTES_GLOBAL_CUR 0x10u /* fc_run_election_series: the replay keeps each chain's
+                                    current assignment in a global row instead of LDS -- the path a
+                                    graph too large for the default dynamic LDS limit takes; same
+                                    output (a cross-check)                                      */
 
 typedef struct fc_graph fc_graph;
 typedef struct fc_run fc_run;
@@ -382,6 +386,44 @@ int fc_run_frame_series(fc_run *r, int32_t c0, int32_t nc, int32_t n_frame, cons
 int fc_run_frame_series_changes(fc_run *r, int32_t c0, int32_t nc, int32_t n_frame, const int32_t *frame_u,
                                 const int32_t *frame_v, const double *mid_xy, double cx, double cy, int64_t cap,
                                 int64_t *offsets, int64_t *t, double *slope, double *angle);
+/* ---- election series: what the sampled plans do (gerrychain's Tally / Election updaters and the
+ * seats / efficiency-gap outlier histograms), by a device replay of the flip log against node
+ * columns.  Flip runs with FC_DIAG_SERIES, any k.
+ * Over the window's yields t = series_t0 .. steps, with a_t the assignment at yield t:
+ *   S_t[d][j]       = sum of node_cols[u][j] over the nodes u with a_t(u) = d;
+ *   tally_now[d][j] = S at the current yield;      tally_sum[d][j] = sum_t S_t[d][j];
+ * and per election e = (A, B) = (col_a[e], col_b[e]), with a_d = S_t[d][A], b_d = S_t[d][B]:
+ *   A wins district d iff a_d > b_d (a tie is won by neither); seats_t = districts A wins;
+ *   seats_hist[e][s] = yields with seats_t = s (s = 0..k); wins_sum[e][d] = yields in which A wins d;
+ *   gap_t = sum_d g(a_d, b_d), g(a, b) = 3b - a if a > b, b - 3a if a < b, 0 on a tie: the
+ *           efficiency gap (wasted_B - wasted_A) / total in units of 1 / (2 total votes),
+ *           positive when it favours A (gerrychain's efficiency_gap is gap_t / (2 V));
+ *   gap_sum[e] = sum_t gap_t;  gap_hist[e][i] = yields with i = the number of gap_edges <= gap_t
+ *           (numpy searchsorted(gap_edges, gap_t, side="right")), i = 0..n_gap_edges.
+ * All exact integers; every histogram row of a chain sums to its window's yields.
+ *
+ * fc_run_set_elections copies and uploads node_cols [n * n_cols] (1 <= n_cols <= 8; values >= 0,
+ * every column total <= 2^31 - 1), the elections (0 <= n_elections <= 4: 0 keeps the tallies
+ * only; col_a[e] != col_b[e], both below n_cols) and the strictly ascending gap_edges
+ * (0 <= n_gap_edges <= 256; 0: no gap histogram).  Callable again to replace them.  The columns
+ * are not trajectory state: checkpoint blobs do not hold them (and are byte for byte what they
+ * were), so a restored run needs fc_run_set_elections again.
+ * fc_run_election_series fills the outputs of chains [c0, c0 + nc) (any may be NULL to skip it)
+ * and synchronises.  FC_ERR_ARG without FC_DIAG_SERIES, before fc_run_set_elections, for a bad
+ * chain range, for gap_hist without edges, for a window of 2^30 yields or more, or when a chain's
+ * log overflowed event_cap; FC_ERR_UNSUPPORTED for ReCom runs (no flip log). */
+int fc_run_set_elections(fc_run *r, int32_t n_cols, const int32_t *node_cols, int32_t n_elections,
+                         const int32_t *col_a, const int32_t *col_b, int32_t n_gap_edges, const int64_t *gap_edges);
+int fc_run_election_series(fc_run *r, int32_t c0, int32_t nc,
+                           int64_t *tally_now, int64_t *tally_sum,  /* [nc * k * n_cols]                     */
+                           int64_t *seats_hist,                      /* [nc * n_elections * (k + 1)]          */
+                           int64_t *wins_sum,                        /* [nc * n_elections * k]                */
+                           int64_t *gap_sum,                         /* [nc * n_elections]                    */
+                           int64_t *gap_hist);                       /* [nc * n_elections * (n_gap_edges + 1)] */
+/* The per-yield rule of one election, by the code the device runs: a, b [k] the districts'
+ * tallies of the two columns (0 <= a, b <= 2^31 - 1, 1 <= k <= 32); *seats = districts A wins,
+ * *gap = sum_d g(a_d, b_d).  Either output may be NULL.  Pure host function. */
+int fc_election_eval(int32_t k, const int64_t *a, const int64_t *b, int32_t *seats, int64_t *gap);
 /* Page-lock (pin) a caller's host buffer for faster device-to-host copies of the readers above
  * (hipHostRegister); unregister before freeing it. */
 int fc_host_register(void *ptr, int64_t bytes);
