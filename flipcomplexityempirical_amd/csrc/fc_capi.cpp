@@ -525,7 +525,7 @@ int fc_run_steps(fc_run *r, int64_t n_steps, int64_t max_draws, void *hip_stream
             HIP_TRY(hipMemsetAsync(r->d_eta + k.eta_parity, 0, sizeof(uint32_t), s));
         }
         const int e = r->p.k == 2 ? fc::launch_flip2(k, r->g.ring_max, s, r->kname, sizeof r->kname)
-                                    : fc::launch_flip_k2(k, r->g.ring_max, s, r->kname, sizeof r->kname);
+                                    : fc::launch_flipk(k, r->g.ring_max, s, r->kname, sizeof r->kname);
         if (e != 0) return fail(FC_ERR_HIP, std::string("flip kernel launch: ") + hipGetErrorString((hipError_t)e));
         if (k.tl_len) {  // the launch's logged tallies, applied and the logs emptied
             const int er = fc::launch_tally_reduce(k, r->g.ring_max, s);

@@ -38,6 +38,21 @@ __device__ __forceinline__ uint64_t lane_range(int lo, int hi) { return bits_bel
 __device__ __forceinline__ int rl32(int x, int lane) { return __builtin_amdgcn_readlane(x, lane); }
 __device__ __forceinline__ uint32_t rlu(uint32_t x, int lane) { return (uint32_t)__builtin_amdgcn_readlane((int)x, lane); }
 
+__device__ __forceinline__ int64_t rl64(int64_t x, int lane) {
+    const uint32_t lo = rlu((uint32_t)x, lane), hi = rlu((uint32_t)((uint64_t)x >> 32), lane);
+    return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+// each argument <- its sum over the 64 lanes, in every lane (the arguments' steps interleaved)
+template <typename... T>
+__device__ __forceinline__ void wave_sum64_all(T &...x) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) ((x += __shfl_xor((long long)x, off)), ...);
+}
+__device__ __forceinline__ int64_t wave_sum64(int64_t x) {
+    wave_sum64_all(x);
+    return x;
+}
+
 __device__ __forceinline__ int count_below(uint64_t m) {  // set bits of m below this lane
     return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
 }
@@ -597,4 +612,13 @@ __device__ __attribute__((noinline)) inline int64_t geom_wait_of(uint32_t x0, ui
 }
 
 }  // namespace dev
+
+// Host: launch `kern` with `lds` bytes of dynamic LDS per workgroup (above 64 KB the kernel's
+// limit has to be raised first).  The caller reads hipGetLastError().
+template <typename P>
+inline void launch_lds(void (*kern)(P), dim3 grid, dim3 block, size_t lds, hipStream_t s, const P &p) {
+    if (lds > 65536) (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(kern, grid, block, lds, s, p);
+}
+
 }  // namespace fc

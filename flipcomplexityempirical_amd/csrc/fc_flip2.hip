@@ -32,6 +32,7 @@
 #include "fc_device.h"
 #include "fc_internal.h"
 #include "fc_philox.h"
+#include "fc_tally.h"
 
 namespace fc {
 
@@ -50,282 +51,6 @@ using namespace dev;
 #ifndef FC_PRIO_EVERY_LOG2
 #define FC_PRIO_EVERY_LOG2 4  // profiles/r04p_prio_period_ab.txt: 55.0 ms against 55.4 every 4 batches, 56.3 every batch
 #endif
-// The per-yield tallies of the reference's loop body (grid_chain_sec11.py:367-400) for one
-// accepted state and its run (kind 0: a flushed queue entry -- yield t of the flip, `run` yields,
-// node u | old-district ring bits << 16, |cut| | target << 31, |B|) or for the yields a batch's
-// start state adds right after a flush (kind 1: yields steps0 + 1 .. steps0 + r0 of the state
-// the last flip created; node last_flip | its district << 16, 0xffff: none).  Every update
-// commutes (sums and maxima), so where and in which order they are applied leaves the results
-// bit-identical: inside the flip kernel (a full log) or by tally_reduce after the launch.
-template <int RMAX>
-__device__ __forceinline__ void tally_apply(const KParams &p, int c, int64_t t, int run, uint32_t qv, uint32_t qc,
-                                            uint32_t nbk, int64_t lab0, int64_t lab1) {
-    const int n = p.n;
-    const int cq = (int)(qc & 0x7fffffffu), nbq = (int)(nbk & 0x7fffffffu);
-    if (p.diag & FC_DIAG_HIST) {
-        atomicAdd((unsigned long long *)&p.cut_hist[(size_t)c * (p.n_edges + 1) + cq], (unsigned long long)run);
-        atomicAdd((unsigned long long *)&p.nb_hist[(size_t)c * (n + 1) + nbq], (unsigned long long)run);
-    }
-    const int u = (int)(qv & 0xffffu);
-    if (nbk >> 31) {  // kind 1: the start state's further yields (the per-batch form in flip2_kernel)
-        if ((p.diag & FC_DIAG_FLIPS) && u != 0xffff) {
-            const size_t o = (size_t)c * n + u;
-            atomicMax((unsigned long long *)(p.last_flipped + o), (unsigned long long)(t + run));
-            atomicAdd((unsigned long long *)(p.part_sum + o), (unsigned long long)(((qv >> 16) & 1u ? lab0 - lab1 : lab1 - lab0) * run));
-            atomicAdd((unsigned long long *)(p.num_flips + o), (unsigned long long)run);
-        }
-        return;
-    }
-    const int tg = (int)(qc >> 31);
-    const int64_t lab_t = tg ? lab1 : lab0, lab_o = tg ? lab0 : lab1;
-    const uint32_t up = qv >> 16;  // neighbours in the old district: their edges turn cut
-    if (p.diag & FC_DIAG_FLIPS) {  // the run's share (fc_run_read_flips closes the last run)
-        const size_t o = (size_t)c * n + u;
-        const int64_t t_last = t + run - 1;
-        atomicMax((unsigned long long *)(p.last_flipped + o), (unsigned long long)t_last);
-        atomicAdd((unsigned long long *)(p.part_sum + o), (unsigned long long)((lab_o - lab_t) * t_last));
-        atomicAdd((unsigned long long *)(p.num_flips + o), (unsigned long long)run);
-    }
-    if (p.diag & FC_DIAG_FLIPS_EXACT) {
-        const size_t o = (size_t)c * n + u;
-        atomicAdd((unsigned long long *)(p.flip_count + o), 1ull);
-        atomicAdd((unsigned long long *)(p.occ_acc + o), (unsigned long long)(-(lab_t - lab_o) * t));
-        atomicMax((unsigned long long *)(p.last_accept + o), (unsigned long long)t);
-    }
-    if (p.diag & FC_DIAG_EDGES) {
-        const int4 *er = (const int4 *)(p.ring_eid + (size_t)u * RMAX);
-        int eid[RMAX];
-#pragma unroll
-        for (int j = 0; j < RMAX / 4; ++j) {
-            const int4 e4 = er[j];
-            eid[4 * j] = e4.x;
-            eid[4 * j + 1] = e4.y;
-            eid[4 * j + 2] = e4.z;
-            eid[4 * j + 3] = e4.w;
-        }
-        int64_t *ea = p.edge_acc + (size_t)c * p.n_edges;
-#pragma unroll
-        for (int i = 0; i < RMAX; ++i)
-            if (eid[i] >= 0) atomicAdd((unsigned long long *)(ea + eid[i]), (unsigned long long)(((up >> i) & 1u) ? -t : t));
-    }
-}
-
-// One tally-log entry in 16 B (one coalesced store per lane): dt = t - t0 (< 2^24: launches
-// with the log are at most 2^23 steps), run (< 2^24), |B| (< 2^16), node | ring bits << 16,
-// |cut| (< 2^24), target, kind (0: a queue entry, 1: a start state's further yields).
-__device__ __forceinline__ uint4 tally_pack(int64_t dt, int run, uint32_t qv, uint32_t qc, uint32_t nbk) {
-    const uint32_t r = (uint32_t)run, kind = nbk >> 31;
-    return make_uint4(((uint32_t)dt & 0xffffffu) | (r << 24), (r >> 8) | ((nbk & 0xffffu) << 16), qv,
-                      (qc & 0xffffffu) | ((qc >> 31) << 24) | (kind << 25));
-}
-
-// Apply every chain's tally log and reset it: one workgroup per chain, after the flip kernel on
-// the same stream, so the chain's serial stream never waits on these updates.  Each pass keeps
-// the arrays of its mask (TR_* bits) privatised in LDS -- zeroed, every entry of the log applied
-// with LDS atomics, then added (maxed) into the chain's global rows -- and applies the arrays of
-// `gmask` with global atomics (those too large for any pass).  Global atomics from a separate
-// kernel, for all arrays, took 62 ms per C2 launch: the chains' rows do not stay in L2.
-enum : uint32_t { TR_CUT = 1, TR_NB = 2, TR_EDGE = 4, TR_NF = 8, TR_PS = 16, TR_LF = 32, TR_FC = 64, TR_OCC = 128, TR_LA = 256 };
-constexpr int kTrArrays = 9;
-
-__device__ __forceinline__ int64_t tr_len(const KParams &p, int a) {  // entries of array a per chain
-    return a == 0 ? (int64_t)p.n_edges + 1 : a == 1 ? (int64_t)p.n + 1 : a == 2 ? (int64_t)p.n_edges : (int64_t)p.n;
-}
-__device__ __forceinline__ int64_t *tr_row(const KParams &p, int a, int c) {  // chain c's global row
-    int64_t *b = a == 0 ? p.cut_hist : a == 1 ? p.nb_hist : a == 2 ? p.edge_acc : a == 3 ? p.num_flips
-               : a == 4 ? p.part_sum : a == 5 ? p.last_flipped : a == 6 ? p.flip_count : a == 7 ? p.occ_acc : p.last_accept;
-    return b + (size_t)c * (size_t)tr_len(p, a);
-}
-
-template <int RMAX>
-__global__ __launch_bounds__(1024) void tally_reduce_kernel(KParams p, uint32_t lmask, uint32_t gmask, int last) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    unsigned long long *acc = (unsigned long long *)smem;
-    const int c = (int)blockIdx.x;
-    const int tid = (int)threadIdx.x, nt = (int)blockDim.x;
-    const int64_t len = p.tl_len[c];
-    const int64_t lab0 = p.labels[0], lab1 = p.labels[1];
-    // LDS offsets (in entries) of the arrays of this pass, in TR order
-    int64_t off[kTrArrays];
-    int64_t tot = 0;
-#pragma unroll
-    for (int a = 0; a < kTrArrays; ++a) {
-        off[a] = tot;
-        if ((lmask >> a) & 1u) tot += tr_len(p, a);
-    }
-    for (int64_t i = tid; i < tot; i += nt) acc[i] = 0ull;
-    __syncthreads();
-    const uint4 *lg = (const uint4 *)p.tl + (size_t)c * (size_t)p.tl_cap;
-    const int64_t t0 = p.tl_t0[c];
-    // one update: LDS when the array is in this pass, global when it is in gmask
-    auto add = [&](int a, int64_t i, int64_t v) {
-        if ((lmask >> a) & 1u) atomicAdd(acc + off[a] + i, (unsigned long long)v);
-        else if ((gmask >> a) & 1u) atomicAdd((unsigned long long *)(tr_row(p, a, c) + i), (unsigned long long)v);
-    };
-    auto mx = [&](int a, int64_t i, int64_t v) {
-        if ((lmask >> a) & 1u) atomicMax(acc + off[a] + i, (unsigned long long)v);
-        else if ((gmask >> a) & 1u) atomicMax((unsigned long long *)(tr_row(p, a, c) + i), (unsigned long long)v);
-    };
-    const uint32_t want = lmask | gmask;
-    // kU entries per thread in flight: their log loads, then their ring-edge loads, are issued
-    // together (2.24 -> 2.11 ms per C2 launch; contiguous stretches per thread instead, so one
-    // instruction's lanes carry entries from 64 stretches of the launch: 2.54 ms)
-    constexpr int kU = 8;
-    const bool edges = (want & TR_EDGE) != 0;
-    for (int64_t b0 = tid; b0 < len; b0 += (int64_t)nt * kU) {
-        uint4 e[kU];
-#pragma unroll
-        for (int k = 0; k < kU; ++k) {
-            const int64_t i = b0 + (int64_t)k * nt;
-            e[k] = i < len ? lg[i] : make_uint4(0u, 0u, 0u, 0u);
-        }
-        int4 er[kU][RMAX / 4];
-#pragma unroll
-        for (int k = 0; k < kU; ++k) {
-            const int64_t i = b0 + (int64_t)k * nt;
-            const bool need = edges && i < len && !((e[k].w >> 25) & 1u);
-            const int4 *rp = (const int4 *)(p.ring_eid + (size_t)(e[k].z & 0xffffu) * RMAX);
-#pragma unroll
-            for (int j = 0; j < RMAX / 4; ++j) er[k][j] = need ? rp[j] : make_int4(-1, -1, -1, -1);
-        }
-#pragma unroll
-        for (int k = 0; k < kU; ++k) {
-            if (b0 + (int64_t)k * nt >= len) break;
-            const uint4 ek = e[k];  // (tally_pack)
-            const int64_t t = t0 + (int64_t)(ek.x & 0xffffffu);
-            const int run = (int)((ek.x >> 24) | ((ek.y & 0xffffu) << 8));
-            const uint32_t qv = ek.z, qc = (ek.w & 0xffffffu) | (((ek.w >> 24) & 1u) << 31);
-            const int u = (int)(qv & 0xffffu);
-            if (want & TR_CUT) add(0, (int64_t)(qc & 0x7fffffffu), run);
-            if (want & TR_NB) add(1, (int64_t)(ek.y >> 16), run);
-            if ((ek.w >> 25) & 1u) {  // kind 1 (tally_apply)
-                if (u != 0xffff) {
-                    if (want & TR_LF) mx(5, u, t + run);
-                    if (want & TR_PS) add(4, u, ((qv >> 16) & 1u ? lab0 - lab1 : lab1 - lab0) * run);
-                    if (want & TR_NF) add(3, u, run);
-                }
-                continue;
-            }
-            const int tg = (int)(qc >> 31);
-            const int64_t lab_t = tg ? lab1 : lab0, lab_o = tg ? lab0 : lab1;
-            const int64_t t_last = t + run - 1;
-            if (want & TR_LF) mx(5, u, t_last);
-            if (want & TR_PS) add(4, u, (lab_o - lab_t) * t_last);
-            if (want & TR_NF) add(3, u, run);
-            if (want & TR_FC) add(6, u, 1);
-            if (want & TR_OCC) add(7, u, -(lab_t - lab_o) * t);
-            if (want & TR_LA) mx(8, u, t);
-            if (edges) {
-                const uint32_t up = qv >> 16;
-#pragma unroll
-                for (int j = 0; j < RMAX / 4; ++j) {
-                    const int ev[4] = {er[k][j].x, er[k][j].y, er[k][j].z, er[k][j].w};
-#pragma unroll
-                    for (int q = 0; q < 4; ++q)
-                        if (ev[q] >= 0) add(2, ev[q], ((up >> (4 * j + q)) & 1u) ? -t : t);
-                }
-            }
-        }
-    }
-    __syncthreads();
-    // the pass's sums (maxima) into the chain's rows: one workgroup per chain, so no atomics
-#pragma unroll
-    for (int a = 0; a < kTrArrays; ++a) {
-        if (!((lmask >> a) & 1u)) continue;
-        int64_t *row = tr_row(p, a, c);
-        const int64_t L = tr_len(p, a);
-        const bool is_max = a == 5 || a == 8;
-        // four rows' entries per thread in flight (their loads issued together)
-        for (int64_t b0 = tid; b0 < L; b0 += (int64_t)nt * 4) {
-            int64_t cur[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int64_t i = b0 + (int64_t)k * nt;
-                cur[k] = i < L ? row[i] : 0;
-            }
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int64_t i = b0 + (int64_t)k * nt;
-                if (i >= L) break;
-                const int64_t v = (int64_t)acc[off[a] + i];
-                if (is_max) {
-                    if (v > cur[k]) row[i] = v;
-                } else if (v) {
-                    row[i] = cur[k] + v;
-                }
-            }
-        }
-    }
-    if (last) {
-        __syncthreads();
-        if (tid == 0) p.tl_len[c] = 0;
-    }
-}
-
-int launch_tally_reduce(const KParams &p, int ring_max, void *stream) {
-    if (!p.tl_len || p.n_chains <= 0) return (int)hipSuccess;
-    // the arrays this run keeps, their per-chain bytes, packed greedily into passes of at most
-    // 160 KiB of LDS (sec11 with every tally: one pass of 139 KiB, one 1024-thread workgroup per
-    // CU: the log is read once); an array above 160 KiB goes to global atomics
-    uint32_t have = 0;
-    if (p.diag & FC_DIAG_HIST) have |= TR_CUT | TR_NB;
-    if (p.diag & FC_DIAG_EDGES) have |= TR_EDGE;
-    if (p.diag & FC_DIAG_FLIPS) have |= TR_NF | TR_PS | TR_LF;
-    if (p.diag & FC_DIAG_FLIPS_EXACT) have |= TR_FC | TR_OCC | TR_LA;
-    auto bytes = [&](int a) -> size_t {
-        return 8 * (size_t)(a == 0 ? p.n_edges + 1 : a == 1 ? p.n + 1 : a == 2 ? p.n_edges : p.n);
-    };
-    // the device's LDS per workgroup (gfx950: 160 KiB), queried, not assumed
-    int dev = 0, optin = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&optin, hipDeviceAttributeSharedMemPerBlockOptin, dev) != hipSuccess || optin <= 0)
-        optin = 65536;
-    const size_t kPass = (size_t)optin, kMaxLds = (size_t)optin;
-    std::vector<std::pair<uint32_t, size_t>> passes;
-    uint32_t gmask = 0;
-    for (int a = 0; a < kTrArrays; ++a) {
-        if (!((have >> a) & 1u)) continue;
-        const size_t b = bytes(a);
-        if (b > kMaxLds) {
-            gmask |= 1u << a;
-            continue;
-        }
-        bool put = false;
-        for (auto &ps : passes)
-            if (ps.second + b <= std::max(kPass, b)) {
-                ps.first |= 1u << a;
-                ps.second += b;
-                put = true;
-                break;
-            }
-        if (!put) passes.emplace_back(1u << a, b);
-    }
-    if (passes.empty()) passes.emplace_back(0u, 0);
-    for (size_t i = 0; i < passes.size(); ++i) {
-        size_t lds = passes[i].second;
-        uint32_t lmask = passes[i].first, g = i == 0 ? gmask : 0u;
-        const int last = i + 1 == passes.size() ? 1 : 0;
-        const void *fn = ring_max <= 8 ? (const void *)tally_reduce_kernel<8> : (const void *)tally_reduce_kernel<16>;
-        if (lds > 65536 &&
-            hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-            // the device refuses this much dynamic LDS: the pass's arrays take the global atomics
-            (void)hipGetLastError();
-            g |= lmask;
-            lmask = 0;
-            lds = 0;
-        }
-        if (ring_max <= 8)
-            hipLaunchKernelGGL(tally_reduce_kernel<8>, dim3(p.n_chains), dim3(1024), lds, (hipStream_t)stream, p,
-                               lmask, g, last);
-        else
-            hipLaunchKernelGGL(tally_reduce_kernel<16>, dim3(p.n_chains), dim3(1024), lds, (hipStream_t)stream, p,
-                               lmask, g, last);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return (int)e;
-    }
-    return (int)hipSuccess;
-}
-
 template <int RMAX, int NSUB, bool FULL, bool SEARCH, bool XTRA, bool BAND>
 __global__ __launch_bounds__(256, (RMAX == 8 ? 4 : 1)) void flip2_kernel(KParams p) {
     static_assert(FULL || !XTRA, "XTRA is a FULL instance");
@@ -524,8 +249,7 @@ __global__ __launch_bounds__(256, (RMAX == 8 ? 4 : 1)) void flip2_kernel(KParams
             acc_wait += w * (int64_t)q_run[lane];
         }
         tally_flush();
-        wait_cur = (int64_t)(((uint64_t)(uint32_t)rl32((int)(uint32_t)w, qn - 1)) |
-                             ((uint64_t)(uint32_t)rl32((int)(w >> 32), qn - 1) << 32));
+        wait_cur = rl64(w, qn - 1);
         qn = 0;
         compiler_fence();
     };
@@ -1477,11 +1201,7 @@ __global__ __launch_bounds__(256, (RMAX == 8 ? 4 : 1)) void flip2_kernel(KParams
                 trace_len += __popcll(PM);
             }
         }
-        if (!defer && ACCM) {
-            const int la = 63 - __builtin_clzll(ACCM);
-            wait_cur = (int64_t)(((uint64_t)(uint32_t)rl32((int)(uint32_t)my_wait, la)) |
-                                 ((uint64_t)(uint32_t)rl32((int)(my_wait >> 32), la) << 32));
-        }
+        if (!defer && ACCM) wait_cur = rl64(my_wait, 63 - __builtin_clzll(ACCM));
         // draws consumed by the committed slots [0, end)
         int consumed;
         if (target_hit) {
@@ -1532,14 +1252,7 @@ __global__ __launch_bounds__(256, (RMAX == 8 ? 4 : 1)) void flip2_kernel(KParams
         if (BAND && lane < p.words) p.sbits[(size_t)c * p.words + lane] = sb[lane];
     }
     const int64_t cnt_prop = n_prop, cnt_acc = n_acc, cnt_ic = n_ic, cnt_ip = n_ip;  // already wave totals
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        acc_cut += __shfl_xor((long long)acc_cut, off);
-        acc_nb += __shfl_xor((long long)acc_nb, off);
-        acc_wait += __shfl_xor((long long)acc_wait, off);
-        acc_cut2 += __shfl_xor((long long)acc_cut2, off);
-        acc_nb2 += __shfl_xor((long long)acc_nb2, off);
-    }
+    wave_sum64_all(acc_cut, acc_nb, acc_wait, acc_cut2, acc_nb2);
     if (FULL && p.tl_len && lane == 0) p.tl_len[c] = (int64_t)misc[3];
     if (lane == 0) {
         scp->draw = draw;
@@ -1590,13 +1303,10 @@ int launch_flip2(const KParams &p, int ring_max, void *stream, char *name, size_
     const bool search = !p.all_exact || (p.flags & FC_FLAG_FORCE_BFS);
 #define FC_LAUNCH2B(R, S, F, X, Y, B)                                                                      \
     do {                                                                                                    \
-        if (lds > 65536)                                                                                    \
-            (void)hipFuncSetAttribute((const void *)flip2_kernel<R, S, F, X, Y, B>,                         \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                \
         if (name)                                                                                           \
             snprintf(name, name_cap, "fc::flip2_kernel<%d, %d, %s, %s, %s, %s>", R, S, F ? "true" : "false", \
                      X ? "true" : "false", Y ? "true" : "false", B ? "true" : "false");                    \
-        hipLaunchKernelGGL((flip2_kernel<R, S, F, X, Y, B>), grid, block, lds, s, p);                       \
+        launch_lds(flip2_kernel<R, S, F, X, Y, B>, grid, block, lds, s, p);                                 \
     } while (0)
 #define FC_LAUNCH2(R, S, F, X, Y)                        \
     do {                                                 \

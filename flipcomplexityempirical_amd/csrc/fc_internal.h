@@ -164,7 +164,7 @@ struct KParams {
     // chain (two coalesced stores per entry) and applied by tally_reduce after the launch, so
     // the chain's serial stream carries no global atomics (fc_flip2.hip tally_flush).  A full
     // log falls back to the atomics; tl_len is 0 at every launch start (tally_reduce resets it)
-    uint32_t *tl;               // [n_chains * tl_cap][4], 16 B per entry (fc_flip2.hip tally_pack)
+    uint32_t *tl;               // [n_chains * tl_cap][4], 16 B per entry (fc_tally.h tally_pack)
     int64_t *tl_t0;             // [n_chains] yield index at the launch's start (entries hold t - t0)
     int64_t *tl_len;            // [n_chains] entries logged this launch
     int64_t tl_cap;             // entries per chain
@@ -214,12 +214,12 @@ struct RecomParams {
 inline int recom_lds_bytes(int n, int ring_max) { return (ring_max == 8 ? 14 : 15) * ((n + 15) & ~15); }
 int launch_recom(const RecomParams &p, int ring_max, void *stream, char *name, size_t name_cap);
 
-// Launch wrappers (fc_kernels.hip).  Return a hipError_t as int.
+// Launch wrappers.  Return a hipError_t as int.
 // `name` (may be null) receives the launched instance, spelled as rocprofv3 reports it.
-int launch_flip_k2(const KParams &p, int ring_max, void *stream, char *name, size_t name_cap);  // k > 2
-int launch_flip2(const KParams &p, int ring_max, void *stream, char *name, size_t name_cap);    // k = 2
+int launch_flipk(const KParams &p, int ring_max, void *stream, char *name, size_t name_cap);  // k > 2 (fc_kernels.hip)
+int launch_flip2(const KParams &p, int ring_max, void *stream, char *name, size_t name_cap);  // k = 2 (fc_flip2.hip)
 // k = 2 full diagnostics: apply every chain's tally log (KParams tl_*) to the per-chain
-// histograms / per-node / per-edge arrays and reset the logs (fc_flip2.hip)
+// histograms / per-node / per-edge arrays and reset the logs (fc_tally.hip)
 int launch_tally_reduce(const KParams &p, int ring_max, void *stream);
 // chain dealing (fc_deal.hip): order[] = chains by descending key (ctime, the last launch's
 // draws, if `timed`, else the boundary length's complement n - |B|: a short boundary needs

@@ -39,8 +39,8 @@ using namespace dev;
 // district_rule (the district-graph contiguity rule, k > 2): fc_ring.h, shared with the host
 // check tests/native/district_rule_lib.cpp.
 
-// KM = 2: two districts (BI_SIGN, and PAIR with k = 2, which coincide); the outer-face
-// exact rule applies.  KM = 0: k <= 32 districts, PAIR proposals, populations in LDS.  KM = 1:
+// k > 2 only: every two-district run (BI_SIGN, and PAIR with k = 2, which coincide) goes to
+// flip2_kernel (fc_flip2.hip).  KM = 0: k <= 32 districts, PAIR proposals, populations in LDS.  KM = 1:
 // as KM = 0 with the workgroup-cooperative search (p.coop); a separate instance, because the
 // helper waves' code costs the common one its registers (C3: 14 -> 58 spilled VGPRs).  KM = 3:
 // as KM = 0 when the district-graph rule decides every proposal (p.dgraph): no search code.
@@ -54,6 +54,7 @@ using namespace dev;
 #endif
 template <int RMAX, int NSUB, int KM, bool FULL, int MF>
 __global__ __launch_bounds__(256, (RMAX == 8 ? FC_K_WAVES8 : 1)) void flip_kernel(KParams p) {
+    static_assert(KM == 0 || KM == 1 || KM == 3, "KM = 2 is flip2_kernel (fc_flip2.hip)");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = (int)(threadIdx.x & 63u);
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -89,7 +90,7 @@ __global__ __launch_bounds__(256, (RMAX == 8 ? FC_K_WAVES8 : 1)) void flip_kerne
     bs.prof = nullptr;
     // [5][64]: node, word1, word2, draw offset, word3; with the district-graph rule the search
     // never runs and its scratch is not allocated (fc_run_create)
-    uint32_t *slot = KM != 2 && p.dgraph ? (uint32_t *)(T + (2 * RMAX + 2)) : (uint32_t *)(bs.nxt + p.words);
+    uint32_t *slot = p.dgraph ? (uint32_t *)(T + (2 * RMAX + 2)) : (uint32_t *)(bs.nxt + p.words);
     int32_t *popk = (int32_t *)(slot + 5 * 64);    // [32] district populations (KM = 0)
     // PAIR slot bound: fcnt[u] holds nf(u), u's number of foreign districts (its pairs in
     // b_nodes, :151-153), and nfh[j] the nodes with nf = j; the canonical stream draws slots
@@ -104,7 +105,7 @@ __global__ __launch_bounds__(256, (RMAX == 8 ? FC_K_WAVES8 : 1)) void flip_kerne
     int32_t *mcnt = (int32_t *)(q_run + kWaitQK);
     uint32_t *adj = (uint32_t *)(mcnt + p.k * p.k);
     int32_t *ngk = (int32_t *)(adj + 32);
-    const bool dgraph = KM == 3 || (KM != 2 && p.dgraph != 0);  // KM = 3: always, by construction
+    const bool dgraph = KM == 3 || p.dgraph != 0;  // KM = 3: always, by construction
     // KM = 3 multi-flip commit: marks of the members' neighbours, hashed to 2048 bits (1024 for
     // RMAX = 16, which keeps C5's chain at 11 LDS granules; a collision only ends a group early)
     uint32_t *hb = (uint32_t *)(ngk + 32);
@@ -147,7 +148,7 @@ __global__ __launch_bounds__(256, (RMAX == 8 ? FC_K_WAVES8 : 1)) void flip_kerne
             }
         }
         if (lane < 2 * RMAX + 1) T[lane] = p.thresh[(size_t)c * (2 * RMAX + 1) + lane];
-        if (KM != 2 && lane < 32) {
+        if (lane < 32) {
             popk[lane] = p.popk[(size_t)c * 32 + lane];
             nfh[lane] = p.nfh[(size_t)c * kNfh + lane];
         }
@@ -172,7 +173,7 @@ __global__ __launch_bounds__(256, (RMAX == 8 ? FC_K_WAVES8 : 1)) void flip_kerne
     }
     // slot bound of the PAIR draws and its Lemire threshold 2^32 mod wcap (wave-uniform)
     int wcap = p.wmax;
-    if (KM != 2 && p.wdyn) {
+    if (p.wdyn) {
         wave_sync();
         const uint64_t hm = __ballot(lane >= 1 && lane < kNfh && nfh[lane] > 0);
         wcap = hm ? 63 - __builtin_clzll(hm) : 1;
@@ -185,9 +186,11 @@ __global__ __launch_bounds__(256, (RMAX == 8 ? FC_K_WAVES8 : 1)) void flip_kerne
     int64_t trace_len = scp->trace_len;
     int64_t ev_len = scp->ev_len, hit_time = scp->hit_time;
     int cut = scp->cut, nb = scp->nb;
-    int pops0 = scp->pops[0], pops1 = scp->pops[1];
+    // (k > 2 never changes the two-district populations / outer-face counts; read and written back
+    // as the parent did: without them the register allocation of 55 instances moves)
+    const int pops0 = scp->pops[0], pops1 = scp->pops[1];
     const int pop_lo = scp->pop_lo, pop_hi = scp->pop_hi;  // this chain's bounds (chain_pop_bounds)
-    int ng0 = scp->ngamma[0], ng1 = scp->ngamma[1];
+    const int ng0 = scp->ngamma[0], ng1 = scp->ngamma[1];
     int64_t wait_cur = scp->wait_cur;
     int last_flip = scp->last_flip;
     int stuck = 0;
@@ -258,21 +261,17 @@ __global__ __launch_bounds__(256, (RMAX == 8 ? FC_K_WAVES8 : 1)) void flip_kerne
             const int v = (int)(m >> 32);
             bool ok = inrange && (uint32_t)m >= p.lemire_thresh;
             bool hit;
-            if constexpr (KM != 2) {
-                // the draw's district slot r (word 3, exact Lemire over wmax) can only name a
-                // foreign district if r < fcnt[v] (foreign neighbours >= foreign districts):
-                // slots beyond are non-proposals whatever 1b would find, so they take no slot
-                // (a slot rejected by the Lemire map never proposes: not a non-hit either)
-                const uint64_t mw = (uint64_t)w.x3 * (uint64_t)(uint32_t)wcap;
-                ok = ok && (uint32_t)mw >= wthr;
-                if constexpr (PK) {  // a saturated count passes every slot; 1b decides exactly
-                    const int nfs = (int)(pkb[v] >> 5);
-                    hit = ok && ((int)(mw >> 32) < nfs || nfs == 7);
-                } else {
-                    hit = ok & ((int)(mw >> 32) < (int)fcnt[v]);  // (v < n: no guard, no branch)
-                }
+            // the draw's district slot r (word 3, exact Lemire over wmax) can only name a
+            // foreign district if r < fcnt[v] (foreign neighbours >= foreign districts):
+            // slots beyond are non-proposals whatever 1b would find, so they take no slot
+            // (a slot rejected by the Lemire map never proposes: not a non-hit either)
+            const uint64_t mw = (uint64_t)w.x3 * (uint64_t)(uint32_t)wcap;
+            ok = ok && (uint32_t)mw >= wthr;
+            if constexpr (PK) {  // a saturated count passes every slot; 1b decides exactly
+                const int nfs = (int)(pkb[v] >> 5);
+                hit = ok && ((int)(mw >> 32) < nfs || nfs == 7);
             } else {
-                hit = ok & (fcnt[v] != 0);
+                hit = ok & ((int)(mw >> 32) < (int)fcnt[v]);  // (v < n: no guard, no branch)
             }
             const uint64_t hm = __ballot(hit);
             const int pos = nh + __popcll(hm & bits_below(lane));
@@ -317,110 +316,92 @@ __global__ __launch_bounds__(256, (RMAX == 8 ? FC_K_WAVES8 : 1)) void flip_kerne
         const uint32_t nbr = (uint32_t)(rec.meta >> kMetaNbrShift) & 0xffffu;
         const uint32_t link = (uint32_t)(rec.meta >> kMetaLinkShift) & 0xffffu;
         uint32_t inA = 0;    // ring cells in the old district
-        uint32_t tmask;      // neighbours in the target district
-        int tgt;             // target district
-        bool slot_ok = true;
-        int adv[RMAX];       // districts of the ring cells (KM = 0)
-        int nf_after = 0;    // KM != 2: foreign districts of v after its flip
-        int nf_before = 0;   // ... and before it
-        if constexpr (KM == 2) {
+        uint32_t dall = 0;   // districts among the neighbours
+        int adv[RMAX];       // districts of the ring cells
+        // the raw bytes first, every read issued before the first use (the compiler otherwise
+        // waited on each), then the districts
 #pragma unroll
-            for (int i = 0; i < RMAX; ++i) inA |= (uint32_t)(a[ring_entry<RMAX>(rec.ring, i)] == av) << i;
-            inA &= full;
-            tgt = 1 - av;                       // -1 * assignment, grid_chain_sec11.py:145
-            tmask = nbr & ~inA;
-        } else {
-            uint32_t dall = 0;                  // districts among the neighbours
-            // the raw bytes first, every read issued before the first use (the compiler otherwise
-            // waited on each), then the districts
-#pragma unroll
-            for (int i = 0; i < RMAX; ++i) {
-                const int u = ring_entry<RMAX>(rec.ring, i);
-                adv[i] = PK ? (int)pkb[u] : (int)a[u];
-            }
-#pragma unroll
-            for (int i = 0; i < RMAX; ++i) asm volatile("" : "+v"(adv[i]));
-#pragma unroll
-            for (int i = 0; i < RMAX; ++i) {
-                if constexpr (PK) adv[i] &= 31;
-                inA |= (uint32_t)(adv[i] == av) << i;
-                dall |= (((nbr >> i) & 1u) << adv[i]);
-            }
-            const uint32_t dm = dall & ~(1u << av);  // foreign districts among the neighbours
-            inA &= full;
-            // slow_reversible_propose (:117-130): uniform over (node, district) pairs -- slot
-            // r < wmax by an exact Lemire map of word 3; the r-th foreign district is the target
-            const uint64_t mw = (uint64_t)slot[256 + lane] * (uint64_t)(uint32_t)wcap;
-            const int r = (int)(mw >> 32);
-            slot_ok = (uint32_t)mw >= wthr && r < __popc(dm);
-            uint32_t dd = dm;
-            for (int q = 0; q < r && dd; ++q) dd &= dd - 1u;
-            tgt = dd ? __builtin_ctz(dd) : 0;
-            nf_after = __popc(dall & ~(1u << tgt));
-            nf_before = __popc(dm);
-            tmask = 0;
-#pragma unroll
-            for (int i = 0; i < RMAX; ++i) tmask |= (uint32_t)(adv[i] == tgt) << i;
-            tmask &= nbr;
+        for (int i = 0; i < RMAX; ++i) {
+            const int u = ring_entry<RMAX>(rec.ring, i);
+            adv[i] = PK ? (int)pkb[u] : (int)a[u];
         }
+#pragma unroll
+        for (int i = 0; i < RMAX; ++i) asm volatile("" : "+v"(adv[i]));
+#pragma unroll
+        for (int i = 0; i < RMAX; ++i) {
+            if constexpr (PK) adv[i] &= 31;
+            inA |= (uint32_t)(adv[i] == av) << i;
+            dall |= (((nbr >> i) & 1u) << adv[i]);
+        }
+        const uint32_t dm = dall & ~(1u << av);  // foreign districts among the neighbours
+        inA &= full;
+        // slow_reversible_propose (:117-130): uniform over (node, district) pairs -- slot
+        // r < wmax by an exact Lemire map of word 3; the r-th foreign district is the target
+        const uint64_t mw = (uint64_t)slot[256 + lane] * (uint64_t)(uint32_t)wcap;
+        const int rs = (int)(mw >> 32);
+        const bool slot_ok = (uint32_t)mw >= wthr && rs < __popc(dm);
+        uint32_t dd = dm;
+        for (int q = 0; q < rs && dd; ++q) dd &= dd - 1u;
+        const int tgt = dd ? __builtin_ctz(dd) : 0;    // target district
+        const int nf_after = __popc(dall & ~(1u << tgt));  // foreign districts of v after its flip
+        const int nf_before = __popc(dm);                  // ... and before it
+        uint32_t tmask = 0;  // neighbours in the target district
+#pragma unroll
+        for (int i = 0; i < RMAX; ++i) tmask |= (uint32_t)(adv[i] == tgt) << i;
+        tmask &= nbr;
         const uint32_t nbrA = inA & nbr;
         const int nA = __popc(nbrA);
         const int nT = __popc(tmask);
         const bool isprop = has && (rec.deg - nA) > 0 && slot_ok;
-        bool s_lin, s_cyc;
+        bool s_lin;          // the old neighbours lie in one run of the ring's old-district cells
         {
             const uint32_t rot = Ln ? (((inA >> 1) | (inA << (Ln - 1))) & full) : 0u;
             const uint32_t lk = inA & rot & link;
             s_lin = one_run(nbrA, full & ~lk, full);
-            const uint32_t vlink = (Ln >= 2 && (inA & 1u) && ((inA >> (Ln - 1)) & 1u)) ? (1u << (Ln - 1)) : 0u;
-            s_cyc = one_run(nbrA, full & ~(lk | vlink), full);
         }
-        const bool exact = KM == 2 && (rec.meta & kMetaExact) && !force_bfs;
         const bool gam = (rec.meta & kMetaGamma) != 0;
-        // k > 2 (KM = 0): on an exact interior node (closed, fully linked ring) the flip is
+        // KM = 0, 1: on an exact interior node (closed, fully linked ring) the flip is
         // decided invalid when some district X != A shows up in two of the gaps between the
         // ring's A-runs that hold old neighbours: v + an X-path closes a Jordan curve with
         // old neighbours on both sides.  Anything else multi-run goes to the device BFS.
         bool s_cut = false;
-        if constexpr (KM != 2) {
-            if (dgraph) {
-                // every multi-run case decided locally (district_rule above)
-                s_cut = has && !s_lin && nA > 0 && !district_rule<RMAX>(adv, inA, nbr, Ln, gam, av, adj);
-            } else if (has && !s_lin && nA > 0 && !force_bfs && !gam && (rec.meta & kMetaExact) && (link & full) == full) {
-                uint32_t relA = 0;
-                {
-                    const uint32_t rotA = ((inA << 1) | (inA >> (Ln - 1))) & full;
-                    uint32_t st0 = inA & ~rotA;
-                    const uint32_t a2 = inA | (inA << Ln);
-                    while (st0) {
-                        const int s0 = __builtin_ctz(st0);
-                        st0 &= st0 - 1u;
-                        const int len = __builtin_ctz(~(a2 >> s0));
-                        uint32_t run = ((1u << len) - 1u) << s0;
-                        run = (run | (run >> Ln)) & full;
-                        if (run & nbr) relA |= run;
-                    }
-                }
-                const uint32_t gap = full & ~relA;
-                const uint32_t rotG = ((gap << 1) | (gap >> (Ln - 1))) & full;
-                uint32_t gst = gap & ~rotG;
-                const uint32_t g2 = gap | (gap << Ln);
-                uint32_t seen = 0;
-                while (gst && !s_cut) {
-                    const int s0 = __builtin_ctz(gst);
-                    gst &= gst - 1u;
-                    const int len = __builtin_ctz(~(g2 >> s0));
+        if (dgraph) {
+            // every multi-run case decided locally (district_rule above)
+            s_cut = has && !s_lin && nA > 0 && !district_rule<RMAX>(adv, inA, nbr, Ln, gam, av, adj);
+        } else if (has && !s_lin && nA > 0 && !force_bfs && !gam && (rec.meta & kMetaExact) && (link & full) == full) {
+            uint32_t relA = 0;
+            {
+                const uint32_t rotA = ((inA << 1) | (inA >> (Ln - 1))) & full;
+                uint32_t st0 = inA & ~rotA;
+                const uint32_t a2 = inA | (inA << Ln);
+                while (st0) {
+                    const int s0 = __builtin_ctz(st0);
+                    st0 &= st0 - 1u;
+                    const int len = __builtin_ctz(~(a2 >> s0));
                     uint32_t run = ((1u << len) - 1u) << s0;
-                    run = (run | (run >> Ln)) & full & ~inA;
-                    uint32_t dR = 0;
-                    while (run) {
-                        const int i = __builtin_ctz(run);
-                        run &= run - 1u;
-                        dR |= 1u << dist(ring_entry<RMAX>(rec.ring, i));
-                    }
-                    s_cut = (dR & seen) != 0;
-                    seen |= dR;
+                    run = (run | (run >> Ln)) & full;
+                    if (run & nbr) relA |= run;
                 }
+            }
+            const uint32_t gap = full & ~relA;
+            const uint32_t rotG = ((gap << 1) | (gap >> (Ln - 1))) & full;
+            uint32_t gst = gap & ~rotG;
+            const uint32_t g2 = gap | (gap << Ln);
+            uint32_t seen = 0;
+            while (gst && !s_cut) {
+                const int s0 = __builtin_ctz(gst);
+                gst &= gst - 1u;
+                const int len = __builtin_ctz(~(g2 >> s0));
+                uint32_t run = ((1u << len) - 1u) << s0;
+                run = (run | (run >> Ln)) & full & ~inA;
+                uint32_t dR = 0;
+                while (run) {
+                    const int i = __builtin_ctz(run);
+                    run &= run - 1u;
+                    dR |= 1u << dist(ring_entry<RMAX>(rec.ring, i));
+                }
+                s_cut = (dR & seen) != 0;
+                seen |= dR;
             }
         }
         const int delta = nA - nT;  // cut(S') - cut(S)
@@ -487,32 +468,21 @@ __global__ __launch_bounds__(256, (RMAX == 8 ? FC_K_WAVES8 : 1)) void flip_kerne
         while (pos < end) {
             FC_PROF(6, 1);
             const bool prop = isprop && lane >= pos && lane < end;
-            // contiguity verdict when the other district does / does not touch the outer face
-            bool known = true, okT, okN;
+            // contiguity verdict (known: decided without a search)
+            bool known = true, ok;
             if (st & ST_BD) {
-                okT = okN = (st & ST_BR) != 0;
+                ok = (st & ST_BR) != 0;
             } else if (nA == 0) {
-                okT = okN = false;
-            } else if (exact) {
-                okT = s_lin;
-                okN = gam ? s_cyc : s_lin;
-            } else if (KM != 2 && s_cut) {
-                okT = okN = false;
-            } else if (KM != 2 && dgraph) {
-                okT = okN = true;  // one run, or the district rule found the pieces joined
+                ok = false;
+            } else if (s_cut) {
+                ok = false;
+            } else if (dgraph) {
+                ok = true;  // one run, or the district rule found the pieces joined
             } else {
                 known = s_lin;
-                okT = okN = s_lin;
+                ok = s_lin;
             }
-            int pa, pb;
-            if constexpr (KM == 2) {
-                pa = av ? pops1 : pops0;
-                pb = av ? pops0 : pops1;
-            } else {
-                pa = popk[av];
-                pb = popk[tgt];
-            }
-            const bool ok = ((av ? ng0 : ng1) > 0) ? okT : okN;
+            const int pa = popk[av], pb = popk[tgt];
             const bool popok = (pa - pv >= pop_lo) && (pb + pv <= pop_hi);
             const bool valid = prop && known && ok && popok;
             // ---- one event at a time: the first acceptance or undecided slot -----------------
@@ -965,7 +935,7 @@ __global__ __launch_bounds__(256, (RMAX == 8 ? FC_K_WAVES8 : 1)) void flip_kerne
             const bool gamf = (pkf >> 27) & 1u;
             const int df = (int)((pk3f >> 16) & 0x3fu) - 32;
             const int pvf = rl32(pv, f);
-            const uint32_t inAf = pk2f & 0xffffu, nbrf = pk2f >> 16, tmf = pk3f & 0xffffu;
+            const uint32_t nbrf = pk2f >> 16;
             uint32_t rw[RMAX / 2];
 #pragma unroll
             for (int k2 = 0; k2 < RMAX / 2; ++k2) rw[k2] = rlu(rec.ring[k2], f);
@@ -978,81 +948,69 @@ __global__ __launch_bounds__(256, (RMAX == 8 ? FC_K_WAVES8 : 1)) void flip_kerne
             bool enter = false, leave = false, grew = false;
             bool wcap_chg = false;
             int dpair = 0;  // FC_FLAG_NB_PAIRS: this lane's change of the (node, district) pair count
-            if constexpr (KM == 2) {
-                // foreign-neighbour counts: u sees v leave A (+1 if u in A) and join t (-1 if u in t)
-                const int dlt = (int)((inAf >> lane) & 1u) - (int)((tmf >> lane) & 1u);
-                if (is_nbr && dlt != 0) {
-                    const int old = fcnt[my_e];
-                    fcnt[my_e] = (uint8_t)(old + dlt);
-                    enter = dlt > 0 && old == 0;
-                    leave = dlt < 0 && old == 1;
+            // foreign districts nf(u) of vf's neighbours, recounted on the new state (v
+            // leaving A can drop A from u's foreign set, joining T add T), and vf's own
+            // from the evaluation; nfh follows every change, and with it the slot bound
+            const int nf_af = (int)((pk3f >> 22) & 31u), nf_bf = (int)(pk3f >> 27);
+            if (lane == 0) {
+                if constexpr (PK) pkb[vf] = (uint8_t)(tf | ((nf_af < 7 ? nf_af : 7) << 5));
+                else a[vf] = (int8_t)tf;
+            }
+            compiler_fence();
+            if (is_nbr) {
+                const NodeRec<RMAX> ru = G[my_e];
+                const int au = dist(my_e);
+                const uint32_t nbu = (uint32_t)(ru.meta >> kMetaNbrShift) & 0xffffu;
+                uint32_t du = 0, du0 = 0;  // districts among u's neighbours after / before the flip
+                // (every ring cell read, the reads issued together; the neighbour bit masks)
+                int xr[RMAX];
+#pragma unroll
+                for (int i = 0; i < RMAX; ++i) {
+                    const int w = ring_entry<RMAX>(ru.ring, i);
+                    xr[i] = PK ? (int)pkb[w] : (int)a[w];
                 }
-                grew = enter;
-            } else {
-                // foreign districts nf(u) of vf's neighbours, recounted on the new state (v
-                // leaving A can drop A from u's foreign set, joining T add T), and vf's own
-                // from the evaluation; nfh follows every change, and with it the slot bound
-                const int nf_af = (int)((pk3f >> 22) & 31u), nf_bf = (int)(pk3f >> 27);
-                if (lane == 0) {
-                    if constexpr (PK) pkb[vf] = (uint8_t)(tf | ((nf_af < 7 ? nf_af : 7) << 5));
-                    else a[vf] = (int8_t)tf;
+#pragma unroll
+                for (int i = 0; i < RMAX; ++i) asm volatile("" : "+v"(xr[i]));
+#pragma unroll
+                for (int i = 0; i < RMAX; ++i) {
+                    const int w = ring_entry<RMAX>(ru.ring, i);
+                    const uint32_t ni = (nbu >> i) & 1u;
+                    const int xw = PK ? (xr[i] & 31) : xr[i];
+                    du |= ni << xw;
+                    du0 |= ni << (w == vf ? Af : xw);
                 }
+                const int nfn = __popc(du & ~(1u << au));
+                // the old count: exact from the ring when packed (a stored 7 may stand for more)
+                const int old = PK ? __popc(du0 & ~(1u << au)) : (int)fcnt[my_e];
+                if (nfn != old) {
+                    if constexpr (PK) pkb[my_e] = (uint8_t)(au | ((nfn < 7 ? nfn : 7) << 5));
+                    else fcnt[my_e] = (uint8_t)nfn;
+                    atomicSub(&nfh[old], 1);
+                    atomicAdd(&nfh[nfn], 1);
+                }
+                enter = old == 0 && nfn > 0;
+                leave = old > 0 && nfn == 0;
+                grew = nfn > old;
+                dpair = nfn - old;
+            }
+            if (lane == 0) {
+                // vf's own count: before / after from its evaluation (its view was current)
+                const int old = PK ? nf_bf : (int)fcnt[vf];
+                dpair += nf_af - old;
+                if (nf_af != old) {
+                    if constexpr (!PK) fcnt[vf] = (uint8_t)nf_af;
+                    atomicSub(&nfh[old], 1);
+                    atomicAdd(&nfh[nf_af], 1);
+                }
+            }
+            if (p.wdyn) {
                 compiler_fence();
-                if (is_nbr) {
-                    const NodeRec<RMAX> ru = G[my_e];
-                    const int au = dist(my_e);
-                    const uint32_t nbu = (uint32_t)(ru.meta >> kMetaNbrShift) & 0xffffu;
-                    uint32_t du = 0, du0 = 0;  // districts among u's neighbours after / before the flip
-                    // (every ring cell read, the reads issued together; the neighbour bit masks)
-                    int xr[RMAX];
-#pragma unroll
-                    for (int i = 0; i < RMAX; ++i) {
-                        const int w = ring_entry<RMAX>(ru.ring, i);
-                        xr[i] = PK ? (int)pkb[w] : (int)a[w];
-                    }
-#pragma unroll
-                    for (int i = 0; i < RMAX; ++i) asm volatile("" : "+v"(xr[i]));
-#pragma unroll
-                    for (int i = 0; i < RMAX; ++i) {
-                        const int w = ring_entry<RMAX>(ru.ring, i);
-                        const uint32_t ni = (nbu >> i) & 1u;
-                        const int xw = PK ? (xr[i] & 31) : xr[i];
-                        du |= ni << xw;
-                        du0 |= ni << (w == vf ? Af : xw);
-                    }
-                    const int nfn = __popc(du & ~(1u << au));
-                    // the old count: exact from the ring when packed (a stored 7 may stand for more)
-                    const int old = PK ? __popc(du0 & ~(1u << au)) : (int)fcnt[my_e];
-                    if (nfn != old) {
-                        if constexpr (PK) pkb[my_e] = (uint8_t)(au | ((nfn < 7 ? nfn : 7) << 5));
-                        else fcnt[my_e] = (uint8_t)nfn;
-                        atomicSub(&nfh[old], 1);
-                        atomicAdd(&nfh[nfn], 1);
-                    }
-                    enter = old == 0 && nfn > 0;
-                    leave = old > 0 && nfn == 0;
-                    grew = nfn > old;
-                    dpair = nfn - old;
-                }
-                if (lane == 0) {
-                    // vf's own count: before / after from its evaluation (its view was current)
-                    const int old = PK ? nf_bf : (int)fcnt[vf];
-                    dpair += nf_af - old;
-                    if (nf_af != old) {
-                        if constexpr (!PK) fcnt[vf] = (uint8_t)nf_af;
-                        atomicSub(&nfh[old], 1);
-                        atomicAdd(&nfh[nf_af], 1);
-                    }
-                }
-                if (p.wdyn) {
-                    compiler_fence();
-                    const uint64_t hm = __ballot(lane >= 1 && lane < kNfh && nfh[lane] > 0);
-                    const int wn = hm ? 63 - __builtin_clzll(hm) : 1;
-                    if (wn != wcap) {  // later draws of the batch map to other slots: end it after f
-                        wcap = wn;
-                        wthr = (0u - (uint32_t)wcap) % (uint32_t)wcap;
-                        wcap_chg = true;
-                    }
+                const uint64_t hm = __ballot(lane >= 1 && lane < kNfh && nfh[lane] > 0);
+                const int wn = hm ? 63 - __builtin_clzll(hm) : 1;
+                if (wn != wcap) {  // later draws of the batch map to other slots: end it after f
+                    wcap = wn;
+                    wthr = (0u - (uint32_t)wcap) % (uint32_t)wcap;
+                    wcap_chg = true;
                 }
             }
             FC_STAMP(t_g2);
@@ -1061,8 +1019,7 @@ __global__ __launch_bounds__(256, (RMAX == 8 ? FC_K_WAVES8 : 1)) void flip_kerne
             // slots any node whose foreign-district count grew (its slot may now fall below it)
             uint64_t ent = __ballot(grew);
             int dnb = __popcll(__ballot(enter)) - __popcll(__ballot(leave));
-            if constexpr (KM != 2)
-                if (p.nb_pairs) dnb = rl32(wave_scan_incl(dpair), 63);
+            if (p.nb_pairs) dnb = rl32(wave_scan_incl(dpair), 63);
             // district-graph tables: the pairs {vf, w} of vf's face-adjacent cells w move from
             // (Af, a[w]) to (tf, a[w]); a count crossing 0 flips an adjacency bit (as does an
             // outer-face node crossing between districts), which may change the verdict of a
@@ -1102,17 +1059,8 @@ __global__ __launch_bounds__(256, (RMAX == 8 ? FC_K_WAVES8 : 1)) void flip_kerne
             FC_STAMP(t_g4);
             FC_PROF(8, t_g4 - t_g0);
             if (lane == 0) {
-                if constexpr (KM == 2) {
-                    a[vf] = (int8_t)tf;
-                    fcnt[vf] = (uint8_t)(__popc(nbrf) - __popc(tmf));
-                } else {
-                    popk[Af] -= pvf;
-                    popk[tf] += pvf;
-                }
-            }
-            if constexpr (KM == 2) {
-                if (Af == 0) { pops0 -= pvf; pops1 += pvf; } else { pops1 -= pvf; pops0 += pvf; }
-                if (gamf) { if (Af == 0) { --ng0; ++ng1; } else { --ng1; ++ng0; } }
+                popk[Af] -= pvf;
+                popk[tf] += pvf;
             }
             cut += df;
             nb += dnb;
@@ -1390,7 +1338,7 @@ __global__ __launch_bounds__(256, (RMAX == 8 ? FC_K_WAVES8 : 1)) void flip_kerne
                 gf[i] = ((const uint4 *)fcnt)[i];
             }
         }
-        if (KM != 2 && lane < 32) {
+        if (lane < 32) {
             p.popk[(size_t)c * 32 + lane] = popk[lane];
             p.nfh[(size_t)c * kNfh + lane] = nfh[lane];
         }
@@ -1442,7 +1390,7 @@ __global__ __launch_bounds__(256, (RMAX == 8 ? FC_K_WAVES8 : 1)) void flip_kerne
     }
 }
 
-int launch_flip_k2(const KParams &p, int ring_max, void *stream, char *name, size_t name_cap) {
+int launch_flipk(const KParams &p, int ring_max, void *stream, char *name, size_t name_cap) {
     // one chain (wave) per workgroup, as in fc_flip2.hip (C3 on one MI355X: 1.35e9 proposals/s
     // against 1.29e9 with four chains per workgroup); tune_chains_per_block = 2 / 4 restores larger ones
     const int wpb = p.wpb;  // fc_params.tune_chains_per_block (resolved by fc_run_create)
@@ -1457,13 +1405,10 @@ int launch_flip_k2(const KParams &p, int ring_max, void *stream, char *name, siz
     const bool full = p.tape || p.trace || (p.diag & ~(uint32_t)FC_DIAG_WAIT) || p.hit_lo <= p.hit_hi;
 #define FC_LAUNCHM(R, S, K, F, M)                                                                       \
     do {                                                                                                \
-        if (lds > 65536)                                                                                \
-            (void)hipFuncSetAttribute((const void *)flip_kernel<R, S, K, F, M>,                         \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);            \
         if (name)                                                                                       \
             snprintf(name, name_cap, "fc::flip_kernel<%d, %d, %d, %s, %d>", R, S, K, F ? "true" : "false", \
                      (int)(M));                                                                         \
-        hipLaunchKernelGGL((flip_kernel<R, S, K, F, M>), grid, block, lds, s, p);                       \
+        launch_lds(flip_kernel<R, S, K, F, M>, grid, block, lds, s, p);                                 \
     } while (0)
     // the multi-flip instance: district-graph rule, when the run asks for it
     // (1: hashed marks; 2: exact marks, when fc_run_create found room for a byte per node)

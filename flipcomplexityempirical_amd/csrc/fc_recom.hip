@@ -44,12 +44,6 @@ __device__ __forceinline__ uint64_t mulhi64(uint64_t r, uint64_t n) { return __u
 
 __device__ __forceinline__ uint32_t word4(const uint4 &w, int t) { return t == 0 ? w.x : t == 1 ? w.y : t == 2 ? w.z : w.w; }
 
-__device__ __forceinline__ int64_t wave_sum64(int64_t x) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor((long long)x, off);
-    return x;
-}
-
 // Index of the k-th set flag over items [0, count) split into per-lane contiguous chunks:
 // `flag(i)` is evaluated twice per item of the owning lane (count, then locate).
 template <typename F>
@@ -617,11 +611,8 @@ int launch_recom(const RecomParams &p, int ring_max, void *stream, char *name, s
     const dim3 grid(blocks), block(kWave * wpb);
 #define FC_LAUNCH_R(R)                                                                                       \
     do {                                                                                                     \
-        if (lds > 65536)                                                                                     \
-            (void)hipFuncSetAttribute((const void *)recom_kernel<R>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                      (int)lds);                                                            \
         if (name) snprintf(name, name_cap, "fc::recom_kernel<%d>", R);                                         \
-        hipLaunchKernelGGL((recom_kernel<R>), grid, block, lds, s, p);                                        \
+        launch_lds(recom_kernel<R>, grid, block, lds, s, p);                                                  \
     } while (0)
     if (ring_max == 8) FC_LAUNCH_R(8);
     else if (ring_max == 16) FC_LAUNCH_R(16);

@@ -13,7 +13,7 @@ res = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-s
                      capture_output=True, text=True)
 rows, cur = [], None
 for line in res.stderr.splitlines():
-    m = re.search(r"remark: ([^\[]+?) \[-Rpass", line)
+    m = re.search(r"remark: (.+?) \[-Rpass", line)  # (keys such as "ScratchSize [bytes/lane]" hold brackets)
     if not m:
         continue
     key, _, val = m.group(1).partition(":")
@@ -27,4 +27,5 @@ for r in rows:
     if flt in r["name"]:
         print(f'{r["name"]:<60} VGPR {r.get("VGPRs", "?"):>4} AGPR {r.get("AGPRs", "?"):>3} '
               f'vspill {r.get("VGPRs Spill", "?"):>3} sspill {r.get("SGPRs Spill", "?"):>4} '
-              f'scratch {r.get("ScratchSize [bytes/lane]", "?"):>4} occ {r.get("Occupancy [waves/SIMD]", "?")}')
+              f'scratch {r.get("ScratchSize [bytes/lane]", "?"):>4} occ {r.get("Occupancy [waves/SIMD]", "?")} '
+              f'lds {r.get("LDS Size [bytes/block]", "?")} sgpr {r.get("TotalSGPRs", "?")}')
