@@ -47,6 +47,7 @@ EXPORTED = [
     "fc_run_set_ladders", "fc_run_exchange", "fc_run_read_rungs", "fc_run_read_bases", "fc_run_read_rung_stats",
     "fc_ladder_swap_threshold",
     "fc_run_set_elections", "fc_run_election_series", "fc_election_eval",
+    "fc_run_set_shapes", "fc_run_shape_series", "fc_shape_score",
     "fc_run_destroy",
     "fc_device_count", "fc_device_pci_id", "fc_last_error", "fc_build_flags", "fc_build_id",
 ]
@@ -240,6 +241,9 @@ def load(build_if_missing: bool = True, allow_variant: bool = False):
     L.fc_run_set_elections.argtypes = [vp, i32, _P(i32), i32, _P(i32), _P(i32), i32, _P(i64)]
     L.fc_run_election_series.argtypes = [vp, i32, i32, _P(i64), _P(i64), _P(i64), _P(i64), _P(i64), _P(i64)]
     L.fc_election_eval.argtypes = [i32, _P(i64), _P(i64), _P(i32), _P(i64)]
+    L.fc_run_set_shapes.argtypes = [vp, _P(i32), _P(i32), _P(i32), i32, _P(i64)]
+    L.fc_run_shape_series.argtypes = [vp, i32, i32] + [_P(i64)] * 8
+    L.fc_shape_score.argtypes = [i64, i64, _P(i64)]
     L.fc_device_pci_id.argtypes = [i32, ctypes.c_char_p, i32]
     L.fc_run_destroy.argtypes = [vp]
     L.fc_run_destroy.restype = None

@@ -128,6 +128,56 @@ class Election:
         return ElectionResults(self, {party: Tally(col)(partition) for party, col in self.parties_to_columns.items()})
 
 
+class Compactness:
+    """Per-part shape of a partition from integer geometry attributes: node ``area``, node
+    ``exterior`` (the length of a unit's boundary on the outside of the whole region; a node
+    without the attribute has none) and edge ``shared`` (the length two adjacent units share) --
+    gerrychain's ``Tally(area)``, ``perimeter`` and ``polsby_popper`` updaters [gc-0.2] in one.
+    Called on a partition it returns ``{part: {"area", "perimeter", "polsby_popper", "q"}}``:
+    the perimeter is the part's exterior length plus the shared lengths of its cut edges,
+    ``polsby_popper`` the float 4 pi A / P^2 (0.0 for P = 0) and ``q`` the device's integer score
+    ``min(2^20 A // P^2, 2^31 - 1)`` (DESIGN.md §5d).  As an updater of a chain's initial state it
+    makes :meth:`MarkovChain.run` replay the shapes over every yield on the device
+    (``ChainResult.shapes``)."""
+
+    def __init__(self, area: str = "area", exterior: str = "boundary_perim", shared: str = "shared_perim"):
+        self.area, self.exterior, self.shared = area, exterior, shared
+
+    def __call__(self, partition) -> Dict[Any, Dict[str, Any]]:
+        g, a = partition.graph, partition.assignment
+        ar: Dict[Any, int] = {}
+        per: Dict[Any, int] = {}
+        for nd, p in a.items():
+            ar[p] = ar.get(p, 0) + g.nodes[nd][self.area]
+            per[p] = per.get(p, 0) + g.nodes[nd].get(self.exterior, 0)
+        for u, w in g.edges:
+            if a[u] != a[w]:
+                per[a[u]] += g.edges[u, w][self.shared]
+                per[a[w]] += g.edges[u, w][self.shared]
+        return {p: {"area": ar[p], "perimeter": per[p],
+                    "polsby_popper": 4 * math.pi * ar[p] / per[p] ** 2 if per[p] else 0.0,
+                    "q": min((int(ar[p]) << 20) // int(per[p]) ** 2, 2 ** 31 - 1) if per[p] else 0}
+                for p in ar}
+
+    def arrays(self, graph, spec: GraphSpec, edges):
+        """``(area [n], edge_len [E], exterior [n])`` of ``graph`` in the canonical node and edge
+        orders of ``spec`` (``FlipRun.set_shapes``); ValueError for a missing or non-integer value."""
+        area = node_columns(graph, spec.nodes, [self.area])[self.area]
+        ext = np.zeros(spec.n, dtype=np.int64)
+        have = [i for i, nd in enumerate(spec.nodes) if self.exterior in graph.nodes[nd]]
+        if have:
+            ext[have] = node_columns(graph, [spec.nodes[i] for i in have], [self.exterior])[self.exterior]
+        lens = []
+        for u, w in edges:
+            d = graph.edges[spec.nodes[u], spec.nodes[w]]
+            x = d.get(self.shared)
+            if isinstance(x, bool) or not isinstance(x, (int, np.integer)):
+                raise ValueError(f"edge {(spec.nodes[u], spec.nodes[w])!r}: attribute {self.shared!r} = {x!r} "
+                                 "is not an integer")
+            lens.append(int(x))
+        return area, np.asarray(lens, dtype=np.int64), ext
+
+
 def cut_edges(partition):
     """``gerrychain.updaters.cut_edges``: edges (sorted tuples) whose ends are in different parts."""
     a = partition.assignment
@@ -801,7 +851,9 @@ class MarkovChain:
         # Election updaters of the initial state: replayed over every yield on the device from the
         # flip log, so they need the event log whether or not the per-yield lists are kept
         elections = {key: u for key, u in self.initial_state.updaters.items() if isinstance(u, Election)}
-        log = series or bool(elections)
+        # the (first) Compactness updater likewise: district shapes over every yield (§5d)
+        shapes = next((u for u in self.initial_state.updaters.values() if isinstance(u, Compactness)), None)
+        log = series or bool(elections) or shapes is not None
         if log:
             diag |= _lib.FC_DIAG_SERIES
         if corrected:
@@ -815,9 +867,16 @@ class MarkovChain:
             run.set_elections(np.stack([cols[c] for c in col_names], axis=1),
                               [(col_names.index(u.columns[0]), col_names.index(u.columns[1]))
                                for u in elections.values()])
+        if shapes is not None:
+            area, lens, ext = shapes.arrays(self.initial_state.graph, self.cspec.spec, self.edges)
+            run.set_shapes(area, lens, ext)
         if self.total_steps > 1:
             run.steps(self.total_steps - 1)
         res = ChainResult.from_run(self, run, 0)
+        if shapes is not None:
+            ss = run.shape_series(0, 1)
+            res.shapes = {key: ss[key][0].copy() for key in ("area_now", "perim_now", "perim_sum", "pp_now", "pp_sum")}
+            res.shapes.update(pp_min_sum=int(ss["pp_min_sum"][0]), yields=int(ss["yields"][0]))
         if elections:
             es = run.election_series(0, 1)
             res.elections = {}
@@ -891,6 +950,10 @@ class ChainResult:
     # seats_hist [k + 1], wins_sum [k] (parts in label order), gap_sum, tally_sum [k, 2] (the two
     # parties' columns), parties, columns, yields
     elections: Optional[Dict[str, Dict[str, Any]]] = None
+    # from the Compactness updater of the initial state, over all yields: area_now,
+    # perim_now, perim_sum, pp_now, pp_sum [k] (parts in label order; pp in units of
+    # Q = floor(2^20 A / P^2)), pp_min_sum, yields
+    shapes: Optional[Dict[str, Any]] = None
 
     def heatmaps(self, shape=(40, 40), offset=(0, 0)) -> Dict[str, np.ndarray]:
         """The driver's ``A2`` arrays (``grid_chain_sec11.py:431-528``): ``A2[n[0], n[1]]``

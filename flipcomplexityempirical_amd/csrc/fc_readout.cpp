@@ -591,6 +591,141 @@ int fc_run_election_series(fc_run *r, int32_t c0, int32_t nc, int64_t *tally_now
     return FC_OK;
 }
 
+// ---- compactness series (fc_shapes.h, fc_shapes.hip) ---------------------------
+
+int fc_shape_score(int64_t area, int64_t perim, int64_t *q) {
+    if (!q) return fail(FC_ERR_ARG, "fc_shape_score: null argument");
+    if (area < 0 || perim < 0 || area > INT32_MAX || perim > INT32_MAX)
+        return fail(FC_ERR_ARG, "fc_shape_score: area and perim must be in 0 .. 2^31 - 1");
+    *q = fc::shape_score(area, perim);
+    return FC_OK;
+}
+
+int fc_run_set_shapes(fc_run *r, const int32_t *node_area, const int32_t *node_ext, const int32_t *edge_len,
+                      int32_t n_pp_edges, const int64_t *pp_edges) {
+    if (!r || !node_area) return fail(FC_ERR_ARG, "fc_run_set_shapes: null argument");
+    if (r->p.proposal == FC_PROPOSE_RECOM)
+        return fail(FC_ERR_UNSUPPORTED, "fc_run_set_shapes: the compactness series replays the flip log (not ReCom)");
+    if (!r->d_events) return fail(FC_ERR_ARG, "fc_run_set_shapes: FC_DIAG_SERIES not enabled");
+    const int32_t n = r->g.n, E = r->g.n_edges;
+    if (E > 0 && !edge_len) return fail(FC_ERR_ARG, "fc_run_set_shapes: null edge_len");
+    if (n_pp_edges < 0 || n_pp_edges > fc::kShapeMaxEdges)
+        return fail(FC_ERR_ARG, "fc_run_set_shapes: n_pp_edges must be 0..64");
+    if (n_pp_edges > 0 && !pp_edges) return fail(FC_ERR_ARG, "fc_run_set_shapes: null pp_edges");
+    int64_t area = 0, perim = 0;
+    for (int32_t u = 0; u < n; ++u) {
+        if (node_area[u] < 0 || (node_ext && node_ext[u] < 0))
+            return fail(FC_ERR_ARG, "fc_run_set_shapes: negative area or exterior length at node " + std::to_string(u));
+        area += node_area[u];
+        perim += node_ext ? node_ext[u] : 0;
+    }
+    for (int32_t e = 0; e < E; ++e) {
+        if (edge_len[e] < 0) return fail(FC_ERR_ARG, "fc_run_set_shapes: negative length at edge " + std::to_string(e));
+        perim += edge_len[e];
+    }
+    if (area > INT32_MAX) return fail(FC_ERR_ARG, "fc_run_set_shapes: node_area totals over 2^31 - 1");
+    if (perim > INT32_MAX)
+        return fail(FC_ERR_ARG, "fc_run_set_shapes: node_ext and edge_len together total over 2^31 - 1");
+    for (int32_t i = 1; i < n_pp_edges; ++i)
+        if (pp_edges[i] <= pp_edges[i - 1])
+            return fail(FC_ERR_ARG, "fc_run_set_shapes: pp_edges must be strictly ascending");
+    const int32_t W = fc::shapes_row_width(r->g.max_degree);
+    if (W == 0) return fail(FC_ERR_UNSUPPORTED, "fc_run_set_shapes: node degree above 16");
+    if (!fc::shapes_fit_lds(r->npad, r->p.k, n_pp_edges, W))
+        return fail(FC_ERR_UNSUPPORTED,
+                    "fc_run_set_shapes: a chain's image (" +
+                        std::to_string(fc::shapes_lds_bytes(r->npad, r->p.k, n_pp_edges, W)) +
+                        " bytes: assignment, histograms, neighbour rows) does not fit 48 KB of LDS");
+    // the neighbour rows: every canonical edge in the rows of both its ends
+    std::vector<fc::ShapeSlot> rows((size_t)n * W, fc::ShapeSlot{-1, 0});
+    std::vector<int32_t> fill(n, 0);
+    for (int32_t e = 0; e < E; ++e) {
+        const int32_t u = r->g.eu[e], w = r->g.ev[e];
+        rows[(size_t)u * W + fill[u]++] = fc::ShapeSlot{w, edge_len[e]};
+        rows[(size_t)w * W + fill[w]++] = fc::ShapeSlot{u, edge_len[e]};
+    }
+    std::vector<fc::ShapeNode> nodes(n);
+    for (int32_t u = 0; u < n; ++u) nodes[u] = fc::ShapeNode{node_area[u], node_ext ? node_ext[u] : 0};
+    if (int rc = fc_run_sync(r)) return rc;  // a reader of the previous tables may still run
+    r->sh_width = 0;
+    if (int rc = r->d_sh_rows.upload(rows)) return rc;
+    if (int rc = r->d_sh_nodes.upload(nodes)) return rc;
+    if (int rc = r->d_sh_edges.upload(pp_edges, (size_t)n_pp_edges)) return rc;
+    r->sh_n_edges = n_pp_edges;
+    r->sh_width = W;
+    return FC_OK;
+}
+
+int fc_run_shape_series(fc_run *r, int32_t c0, int32_t nc, int64_t *area_now, int64_t *perim_now, int64_t *perim_sum,
+                        int64_t *pp_now, int64_t *pp_sum, int64_t *pp_min_sum, int64_t *pp_hist,
+                        int64_t *pp_min_hist) {
+    if (!r) return fail(FC_ERR_ARG, "fc_run_shape_series: null run");
+    if (r->p.proposal == FC_PROPOSE_RECOM)
+        return fail(FC_ERR_UNSUPPORTED, "fc_run_shape_series: the compactness series replays the flip log (not ReCom)");
+    if (!r->d_events) return fail(FC_ERR_ARG, "fc_run_shape_series: FC_DIAG_SERIES not enabled");
+    if (r->sh_width == 0) return fail(FC_ERR_ARG, "fc_run_shape_series: call fc_run_set_shapes first");
+    if (c0 < 0 || nc < 0 || c0 + nc > r->n_chains) return fail(FC_ERR_ARG, "fc_run_shape_series: chain range");
+    if ((pp_hist || pp_min_hist) && r->sh_n_edges == 0)
+        return fail(FC_ERR_ARG, "fc_run_shape_series: the histograms need pp_edges (fc_run_set_shapes)");
+    if (nc == 0) return FC_OK;
+    std::vector<fc::ChainScalars> sc;
+    if (int rc = download_scalars(r, c0, nc, sc)) return rc;
+    std::vector<int64_t> meta((size_t)3 * nc);
+    for (int32_t i = 0; i < nc; ++i) {
+        if (int rc = check_event_overflow(r, "fc_run_shape_series", c0 + i, sc[i])) return rc;
+        if (sc[i].steps - sc[i].ser_t0 + 1 >= (int64_t(1) << 30))
+            return fail(FC_ERR_ARG, "fc_run_shape_series: chain " + std::to_string(c0 + i) +
+                                        "'s window has 2^30 yields or more; reset the series window more often");
+        meta[i] = sc[i].ev_len;
+        meta[(size_t)nc + i] = sc[i].ser_t0;
+        meta[(size_t)2 * nc + i] = sc[i].steps + 1;
+    }
+    const int32_t k = r->p.k, n_edges = r->sh_n_edges;
+    // the outputs, one after the other in one device buffer
+    const size_t ck = (size_t)nc * k, nbins = (size_t)n_edges + 1;
+    const size_t sz[8] = {ck, ck, ck, ck, ck, (size_t)nc, ck * nbins, (size_t)nc * nbins};
+    size_t off[9] = {0};
+    for (int i = 0; i < 8; ++i) off[i + 1] = off[i] + sz[i];
+    int q;
+    if ((q = r->d_sh_meta.grow(meta.size()))) return q;
+    if ((q = r->d_sh_out.grow(off[8]))) return q;
+    HIP_TRY(hipMemcpyAsync(r->d_sh_meta, meta.data(), meta.size() * 8, hipMemcpyHostToDevice, r->stream));
+    fc::ShapesParams sp{};
+    sp.a0 = r->d_ser_a0;
+    sp.npad = r->npad;
+    sp.n = r->g.n;
+    sp.k = k;
+    sp.events = r->d_events;
+    sp.ev_cap = r->ev_cap;
+    sp.ev_len = r->d_sh_meta;
+    sp.t0 = r->d_sh_meta + nc;
+    sp.t_end = r->d_sh_meta + 2 * (size_t)nc;
+    sp.c0 = c0;
+    sp.nc = nc;
+    sp.rows = r->d_sh_rows;
+    sp.nodes = r->d_sh_nodes;
+    sp.width = r->sh_width;
+    sp.n_edges = n_edges;
+    sp.edges = r->d_sh_edges;
+    int64_t *const d_out = r->d_sh_out;
+    sp.area_now = d_out + off[0];
+    sp.perim_now = d_out + off[1];
+    sp.perim_sum = d_out + off[2];
+    sp.pp_now = d_out + off[3];
+    sp.pp_sum = d_out + off[4];
+    sp.pp_min_sum = d_out + off[5];
+    sp.pp_hist = d_out + off[6];
+    sp.pp_min_hist = d_out + off[7];
+    const int e = fc::launch_shapes(sp, r->stream);
+    if (e) return fail(FC_ERR_HIP, std::string("compactness series: ") + hipGetErrorString((hipError_t)e));
+    int64_t *const host[8] = {area_now, perim_now, perim_sum, pp_now, pp_sum, pp_min_sum, pp_hist, pp_min_hist};
+    for (int i = 0; i < 8; ++i)
+        if (host[i] && sz[i] && (i < 6 || n_edges > 0))
+            HIP_TRY(hipMemcpyAsync(host[i], d_out + off[i], sz[i] * 8, hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    return FC_OK;
+}
+
 int fc_run_read_hist(fc_run *r, int64_t *cut_hist, int64_t *nb_hist) {
     if (!r || !cut_hist || !nb_hist) return fail(FC_ERR_ARG, "fc_run_read_hist: null argument");
     if (!r->d_cut_hist) return fail(FC_ERR_ARG, "fc_run_read_hist: FC_DIAG_HIST not enabled");

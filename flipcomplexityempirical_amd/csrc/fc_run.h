@@ -11,6 +11,7 @@
 #include "fc_internal.h"
 #include "fc_ladder.h"
 #include "fc_plan.h"
+#include "fc_shapes.h"
 #include "fc_votes.h"
 
 namespace fc {
@@ -159,6 +160,13 @@ struct fc_run : fc::RunShape {
     DevBuf<int64_t> d_el_meta;    // per call: ev_len, t0, t_end of the chains read, [nc] each
     DevBuf<int64_t> d_el_out;     // per call: the six outputs, one after the other
     DevBuf<int8_t> d_el_cur;      // per call: current-assignment rows when they are not kept in LDS
+    // compactness series (fc_run_set_shapes; fc_shapes.h, fc_shapes.hip).  sh_width 0: not set
+    int32_t sh_width = 0, sh_n_edges = 0;
+    DevBuf<fc::ShapeSlot> d_sh_rows;   // [n * sh_width] neighbour rows
+    DevBuf<fc::ShapeNode> d_sh_nodes;  // [n]
+    DevBuf<int64_t> d_sh_edges;   // [sh_n_edges]
+    DevBuf<int64_t> d_sh_meta;    // per call: ev_len, t0, t_end of the chains read, [nc] each
+    DevBuf<int64_t> d_sh_out;     // per call: the eight outputs, one after the other
     char kname[96] = {0};       // last launched flip-kernel instance
     // replica exchange (fc_run_set_ladders; fc_ladder.h, fc_exchange.hip).  Slots are flat: ladder
     // l's rung r is slot lad_off[l] + r

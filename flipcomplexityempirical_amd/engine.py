@@ -586,6 +586,55 @@ class FlipRun:
         out["yields"] = (st["steps"] - st["series_t0"] + 1)[c0:c0 + nc].astype(np.int64)
         return out
 
+    # ---- compactness series -------------------------------------------
+    def set_shapes(self, area, edge_len, exterior=None, pp_edges=None) -> "FlipRun":
+        """Attach the units' geometry (``fc_run_set_shapes``): ``area`` ``[n]`` and ``exterior``
+        ``[n]`` (the length of a unit's boundary on the outside of the whole region; None: 0) in
+        canonical node order, ``edge_len`` ``[E]`` (the length two adjacent units share) in
+        canonical edge order, all non-negative int32; ``pp_edges`` the strictly ascending int64 bin
+        edges of the Polsby-Popper histograms in units of ``Q = floor(2**20 A / P**2)`` (at most
+        64; None: no histograms).  Callable again to replace them; a restored run needs it again."""
+        def vec(x, size, what):
+            x = np.asarray(x)
+            if x.shape != (size,) or not np.issubdtype(x.dtype, np.integer):
+                raise ValueError(f"{what} must be {size} integers")
+            if x.size and (x.min() < -2 ** 31 or x.max() > 2 ** 31 - 1):
+                raise ValueError(f"{what} must hold int32 values")  # (the library checks the rest)
+            return np.ascontiguousarray(x, dtype=np.int32)
+        ar = vec(area, self.graph.n, "area")
+        el = vec(edge_len, self.graph.n_edges, "edge_len")
+        ex = None if exterior is None else vec(exterior, self.graph.n, "exterior")
+        edges = np.ascontiguousarray([] if pp_edges is None else pp_edges, dtype=np.int64).reshape(-1)
+        check(_lib.load().fc_run_set_shapes(self.handle, _p(ar, ctypes.c_int32), _p(ex, ctypes.c_int32),
+                                            _p(el, ctypes.c_int32), int(edges.size), _p(edges, ctypes.c_int64)),
+              "fc_run_set_shapes")
+        self._shape_edges = int(edges.size)
+        return self
+
+    def shape_series(self, c0: int = 0, nc: Optional[int] = None) -> Dict[str, np.ndarray]:
+        """District shapes of chains ``c0 .. c0 + nc - 1`` over the series window, replayed on the
+        device from the flip log (``fc_run_shape_series``; include/flipchain.h): ``area_now`` /
+        ``perim_now`` / ``perim_sum`` / ``pp_now`` / ``pp_sum`` ``[nc, k]``, ``pp_min_sum`` ``[nc]``,
+        ``pp_hist`` ``[nc, k, n_edges + 1]`` and ``pp_min_hist`` ``[nc, n_edges + 1]`` (only with
+        ``pp_edges``) and ``yields`` ``[nc]``, the yields of each chain's window.  All int64; the
+        Polsby-Popper score of a ``pp`` value ``Q`` is ``4 pi Q / 2**20``."""
+        nc = self.n_chains - c0 if nc is None else int(nc)
+        n_edges = getattr(self, "_shape_edges", 0)
+        k = self.cfg.k
+        m = max(nc, 0)
+        keys = ("area_now", "perim_now", "perim_sum", "pp_now", "pp_sum", "pp_min_sum", "pp_hist", "pp_min_hist")
+        out = {key: np.zeros((m, k), dtype=np.int64) for key in keys[:5]}
+        out["pp_min_sum"] = np.zeros(m, dtype=np.int64)
+        if n_edges:
+            out["pp_hist"] = np.zeros((m, k, n_edges + 1), dtype=np.int64)
+            out["pp_min_hist"] = np.zeros((m, n_edges + 1), dtype=np.int64)
+        check(_lib.load().fc_run_shape_series(self.handle, int(c0), nc,
+                                              *(_p(out.get(key), ctypes.c_int64) for key in keys)),
+              "fc_run_shape_series")
+        st = self.stats()
+        out["yields"] = (st["steps"] - st["series_t0"] + 1)[c0:c0 + nc].astype(np.int64)
+        return out
+
     # ---- replica exchange (DESIGN.md "Replica exchange") ------------------------------
     def set_ladders(self, ladders: Sequence[Sequence[int]], hist: bool = False) -> "FlipRun":
         """``ladders``: lists of local chain indices, rung 0 first (``fc_run_set_ladders``; once

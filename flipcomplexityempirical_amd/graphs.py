@@ -264,6 +264,16 @@ def grid_graph(nx_: int, ny: int) -> GraphSpec:
     return from_networkx(g, pos={nd: (float(nd[0]), float(nd[1])) for nd in g.nodes()})
 
 
+def unit_square_shapes(spec: GraphSpec):
+    """``(area, edge_len, exterior)`` of a lattice of unit square cells (``grid_graph``, sec11), for
+    ``FlipRun.set_shapes``: area 1 per node, length 1 per edge (canonical edge order), and the
+    sides a cell shares with no neighbour, 4 - degree, on the outside.  All int32."""
+    deg = spec.degree()
+    if spec.n and int(deg.max()) > 4:
+        raise ValueError("unit_square_shapes: a unit square cell has at most 4 neighbours")
+    return (np.ones(spec.n, dtype=np.int32), np.ones(spec.n_edges, dtype=np.int32), (4 - deg).astype(np.int32))
+
+
 def threshold_plan(nodes: Sequence, axis: int, cut: float) -> Dict:
     """±1 plan by ``node[axis] >= cut`` (C1: 10x10 grid, ``x[0] >= 5``)."""
     return {n: (1 if n[axis] >= cut else -1) for n in nodes}

@@ -424,6 +424,56 @@ int fc_run_election_series(fc_run *r, int32_t c0, int32_t nc,
  * tallies of the two columns (0 <= a, b <= 2^31 - 1, 1 <= k <= 32); *seats = districts A wins,
  * *gap = sum_d g(a_d, b_d).  Either output may be NULL.  Pure host function. */
 int fc_election_eval(int32_t k, const int64_t *a, const int64_t *b, int32_t *seats, int64_t *gap);
+/* ---- compactness series: how the sampled plans are shaped (gerrychain's perimeter,
+ * exterior_boundaries, interior_boundaries and polsby_popper updaters), by a device replay of the
+ * flip log against node areas and boundary lengths.  Flip runs with
+ * FC_DIAG_SERIES, any k.  Inputs, per run, not trajectory state:
+ *   node_area[n]  int32 >= 0, total <= 2^31 - 1;
+ *   node_ext[n]   int32 >= 0: the length of the unit's boundary on the outside of the whole region
+ *                 (gerrychain's node attribute boundary_perim); NULL: all 0;
+ *   edge_len[E]   int32 >= 0, in the canonical edge order of fc_graph_edges: the length two
+ *                 adjacent units share (gerrychain's edge attribute shared_perim);
+ *                 sum node_ext + sum edge_len <= 2^31 - 1;
+ *   pp_edges[n_pp_edges]  strictly ascending int64, 0 <= n_pp_edges <= 64; 0: no histograms.
+ * Over the window's yields t = series_t0 .. steps, with a_t the assignment at yield t, for
+ * district d:
+ *   A_t[d] = sum of node_area[u] over the nodes u with a_t(u) = d;
+ *   P_t[d] = sum of node_ext[u] over those nodes + sum of edge_len[e] over the edges e = (u, w)
+ *            with a_t(u) != a_t(w) and d in {a_t(u), a_t(w)}: a cut edge counts once for each of
+ *            its two districts;
+ *   Q_t[d] = min(floor(2^20 A_t[d] / P_t[d]^2), 2^31 - 1), and 0 when P_t[d] = 0: the
+ *            Polsby-Popper score is 4 pi Q / 2^20 (2^20 A < 2^51 and P^2 < 2^62: one unsigned
+ *            64-bit division is exact; an edge q <= Q iff q P^2 <= 2^20 A for P > 0);
+ *   Qmin_t = min over d < k of Q_t[d]: the plan's least compact district.
+ * Outputs per chain, all int64:
+ *   area_now[d], perim_now[d], pp_now[d] = A, P, Q at the current yield;
+ *   perim_sum[d] = sum_t P_t[d];   pp_sum[d] = sum_t Q_t[d];   pp_min_sum = sum_t Qmin_t;
+ *   pp_hist[d][i] = yields with i = the number of pp_edges <= Q_t[d] (numpy
+ *            searchsorted(pp_edges, Q_t[d], side="right")), i = 0..n_pp_edges;
+ *   pp_min_hist[i] = the same for Qmin_t.
+ * All exact integers; every histogram row of a chain sums to its window's yields.
+ *
+ * fc_run_set_shapes validates and uploads the inputs (as per-node neighbour rows).  Callable
+ * again to replace them.  Checkpoint blobs do not hold them (and are byte for byte what they
+ * were), so a restored run needs fc_run_set_shapes again.  FC_ERR_ARG without FC_DIAG_SERIES, for
+ * negative values or totals over 2^31 - 1, for edges that do not ascend or more than 64 of them;
+ * FC_ERR_UNSUPPORTED for ReCom runs (no flip log) and when a chain's image (assignment,
+ * histograms, a chunk's neighbour rows) does not fit 48 KB of LDS.
+ * fc_run_shape_series fills the outputs of chains [c0, c0 + nc) (any may be NULL to skip it) and
+ * synchronises.  FC_ERR_ARG without FC_DIAG_SERIES, before fc_run_set_shapes, for a bad chain
+ * range, for a histogram without edges, for a window of 2^30 yields or more, or when a chain's log
+ * overflowed event_cap; FC_ERR_UNSUPPORTED for ReCom runs. */
+int fc_run_set_shapes(fc_run *r, const int32_t *node_area, const int32_t *node_ext, const int32_t *edge_len,
+                      int32_t n_pp_edges, const int64_t *pp_edges);
+int fc_run_shape_series(fc_run *r, int32_t c0, int32_t nc,
+                        int64_t *area_now, int64_t *perim_now, int64_t *perim_sum, /* [nc * k]   */
+                        int64_t *pp_now, int64_t *pp_sum,                          /* [nc * k]   */
+                        int64_t *pp_min_sum,                                       /* [nc]       */
+                        int64_t *pp_hist,      /* [nc * k * (n_pp_edges + 1)] */
+                        int64_t *pp_min_hist); /* [nc * (n_pp_edges + 1)]     */
+/* The score of one district, by the code the device runs: *q = Q(area, perim) as above.
+ * FC_ERR_ARG for values below 0 or above 2^31 - 1.  Pure host function. */
+int fc_shape_score(int64_t area, int64_t perim, int64_t *q);
 /* Page-lock (pin) a caller's host buffer for faster device-to-host copies of the readers above
  * (hipHostRegister); unregister before freeing it. */
 int fc_host_register(void *ptr, int64_t bytes);
