@@ -191,6 +191,11 @@ int fc_run_create(const fc_graph *gr, const fc_params *p, int32_t n_chains, cons
     if ((rc = r->d_sc.upload(plan.sc))) return rc;
     if ((rc = r->d_thresh.upload(plan.thresh))) return rc;
     if ((rc = r->d_log1mp.upload(r->log1mp))) return rc;
+    {
+        uint32_t keys[fc::kPhiloxKeyWords];
+        fc::philox_round_keys((uint32_t)p->seed, (uint32_t)(p->seed >> 32), keys);
+        if ((rc = r->d_pkeys.upload(keys, fc::kPhiloxKeyWords))) return rc;
+    }
     if ((rc = r->d_labels.upload(r->labels))) return rc;
     if ((rc = r->d_cut_hist.upload(plan.cut_hist))) return rc;
     if ((rc = r->d_nb_hist.upload(plan.nb_hist))) return rc;
@@ -308,7 +313,6 @@ static fc::KParams flip_params(const fc_run *r, int64_t n_steps, int64_t max_dra
     k.seed_lo = (uint32_t)r->p.seed;
     k.seed_hi = (uint32_t)(r->p.seed >> 32);
     k.pop_lo = (int32_t)r->p.pop_lo;
-    k.pop_hi = (int32_t)r->p.pop_hi;
     k.n_steps = n_steps;
     k.max_draws = max_draws > 0 ? max_draws : 65536 * std::max<int64_t>(n_steps, 1);
     k.assign = r->d_assign;
@@ -316,6 +320,7 @@ static fc::KParams flip_params(const fc_run *r, int64_t n_steps, int64_t max_dra
     k.sc = r->d_sc;
     k.thresh = r->d_thresh;
     k.log1mp = r->d_log1mp;
+    k.pkeys = r->d_pkeys;
     k.labels = r->d_labels;
     k.diag = r->p.diag_mask;
     k.flags = r->p.flags;

@@ -86,8 +86,9 @@ __global__ __launch_bounds__(256, (RMAX == 8 ? 4 : 1)) void flip2_kernel(KParams
     // creating draw, |B| after the flip, yields so far); see wait_flush below
     uint64_t *q_d = (uint64_t *)(nmark + npad + 16);
     uint32_t *q_nb = (uint32_t *)(q_d + kWaitQ), *q_run = q_nb + kWaitQ;
-    // FULL: the per-flip tallies of a queued state, applied by the same pass (tally_flush):
-    // node | old-district neighbours (ring bits) << 16, |cut| | target district << 31
+    // q_c: |cut| | target district << 31 (wait_flush forms the state's terms of the sums from it);
+    // FULL: the per-flip tallies of a queued state, applied by the same pass (tally_flush), need
+    // q_v as well: node | old-district neighbours (ring bits) << 16
     uint32_t *q_v = q_run + kWaitQ, *q_c = q_v + kWaitQ;
     // [5]: launch start time, previous launch's pace (read back, not held), yield of the first
     // queued state, FULL: tally-log entries written this launch, the launch's first yield
@@ -109,7 +110,8 @@ __global__ __launch_bounds__(256, (RMAX == 8 ? 4 : 1)) void flip2_kernel(KParams
     }
     ChainScalars *scp = p.sc + c;
     uint64_t draw = scp->draw;
-    int64_t steps = scp->steps;  // index of the current yield
+    // index of the launch's first yield; the current one is steps_in + (n_steps - rem)
+    const int64_t steps_in = scp->steps;
     int64_t trace_len = FULL ? scp->trace_len : 0;
     int64_t ev_len = FULL ? scp->ev_len : 0, hit_time = FULL ? scp->hit_time : 0;
     int cut = scp->cut, nb = scp->nb;
@@ -133,7 +135,16 @@ __global__ __launch_bounds__(256, (RMAX == 8 ? 4 : 1)) void flip2_kernel(KParams
 
     // per-lane accumulators, reduced once per launch
     int64_t acc_cut = 0, acc_nb = 0, acc_wait = 0, acc_cut2 = 0, acc_nb2 = 0;
-    int64_t n_prop = 0, n_acc = 0, n_ic = 0, n_ip = 0;  // wave-uniform (scalar) counters
+    // wave-uniform counters: 32-bit scalar partials, folded every 2^FC_PRIO_EVERY_LOG2 batches (at
+    // most 64 each per batch) into 64-bit totals held by lanes 0-2 of one register pair.  Proposals
+    // are not counted: every committed proposal is a step, invalid by contiguity or invalid by
+    // population, so they are the steps taken plus the two invalid counts (write back)
+    int n_acc = 0, n_ic = 0, n_ip = 0;
+    int64_t cnt64 = 0;
+    auto cnt_fold = [&]() {
+        cnt64 += lane == 0 ? n_acc : lane == 1 ? n_ic : lane == 2 ? n_ip : 0;
+        n_acc = n_ic = n_ip = 0;
+    };
 #ifdef FC_PHASE_PROF
     int64_t *prof_acc = (int64_t *)(base + p.chain_lds_bytes - kProfSlots * 8);
     if (lane < kProfSlots) prof_acc[lane] = 0;
@@ -242,6 +253,16 @@ __global__ __launch_bounds__(256, (RMAX == 8 ? 4 : 1)) void flip2_kernel(KParams
     auto wait_flush = [&]() {
         compiler_fence();
         int64_t w = 0;  // (waits off: 0, as the per-batch form leaves them)
+        if (lane < qn) {
+            // the queued states' shares of the run-length-weighted sums: |cut| and |B| of each
+            // state times the yields it lasted (integer sums: the per-batch terms in another order)
+            const uint64_t run = q_run[lane], cq = q_c[lane] & 0x7fffffffu, nq = q_nb[lane];
+            const uint64_t cr = cq * run, br = nq * run;
+            acc_cut += (int64_t)cr;
+            acc_cut2 += (int64_t)(cr * cq);
+            acc_nb += (int64_t)br;
+            acc_nb2 += (int64_t)(br * nq);
+        }
         if (want_wait && lane < qn) {  // the loads before the tallies' atomics (vmcnt completes in order)
             const uint64_t dq = q_d[lane];
             const Words4 g = philox4x32_10((uint32_t)dq, (uint32_t)(dq >> 32), chain_gid, 1u, p.seed_lo, p.seed_hi);
@@ -256,17 +277,20 @@ __global__ __launch_bounds__(256, (RMAX == 8 ? 4 : 1)) void flip2_kernel(KParams
     int prio = 0;  // bits 0-1: the issue priority set; bits 2 and up: batches since it was last chosen
     if (lane == 0) {
         misc[3] = 0;  // the tally log starts empty (tally_reduce emptied it)
-        misc[4] = (uint64_t)steps;
-        if (FULL && p.tl_t0) p.tl_t0[c] = steps;
+        misc[4] = (uint64_t)steps_in;
+        if (FULL && p.tl_t0) p.tl_t0[c] = steps_in;
         misc[0] = __builtin_amdgcn_s_memrealtime();
         // the previous launch's slowest-chain pace, scaled to this launch (0: none yet)
         const float eta0 = p.eta ? (float)p.eta[p.eta_parity ^ 1] * (float)p.n_steps * (1.0f / 1024.0f) : 0.0f;
         misc[1] = (uint64_t)__float_as_uint(eta0);
     }
     compiler_fence();
+    const PhiloxKeys pkeys0 = (PhiloxKeys)(uintptr_t)p.pkeys;
     while (rem > 0) {
         // re-chosen every 2^FC_PRIO_EVERY_LOG2 batches (it moves slowly; scheduling only)
-        if (p.prio_nb[0] > 0 && ((prio += 4) & (((1 << FC_PRIO_EVERY_LOG2) - 1) << 2)) == 0) {
+        const bool every = ((prio += 4) & (((1 << FC_PRIO_EVERY_LOG2) - 1) << 2)) == 0;
+        if (every) cnt_fold();
+        if (every && p.prio_nb[0] > 0) {
             const int done = (int)p.n_steps - rem;
             const float eta = __uint_as_float((uint32_t)misc[1]);
             int lv;
@@ -321,7 +345,10 @@ __global__ __launch_bounds__(256, (RMAX == 8 ? 4 : 1)) void flip2_kernel(KParams
                     nw[j] = p.tape[((size_t)c * (size_t)p.tape_draws + (inr ? draw + (uint64_t)off : draw)) * 6];
                 }
             } else {
-                const Words4 w = philox4x32_10((uint32_t)q, (uint32_t)(q >> 32), chain_gid, 3u, p.seed_lo, p.seed_hi);
+                // (the round keys: read here, in every batch -- held across the loop they spilled)
+                PhiloxKeys pk = pkeys0;
+                asm volatile("" : "+s"(pk));
+                const Words4 w = philox4x32_10_keys((uint32_t)q, (uint32_t)(q >> 32), chain_gid, 3u, pk);
                 nw[0] = w.x0;
                 nw[1] = w.x1;
                 nw[2] = w.x2;
@@ -444,7 +471,9 @@ __global__ __launch_bounds__(256, (RMAX == 8 ? 4 : 1)) void flip2_kernel(KParams
                 w1 = t[1];
                 w2 = t[2];
             } else {
-                const Words4 g = philox4x32_10((uint32_t)d, (uint32_t)(d >> 32), chain_gid, 0u, p.seed_lo, p.seed_hi);
+                PhiloxKeys pk = pkeys0;
+                asm volatile("" : "+s"(pk));
+                const Words4 g = philox4x32_10_keys((uint32_t)d, (uint32_t)(d >> 32), chain_gid, 0u, pk);
                 w1 = g.x1;
                 w2 = g.x2;
             }
@@ -510,8 +539,8 @@ __global__ __launch_bounds__(256, (RMAX == 8 ? 4 : 1)) void flip2_kernel(KParams
         int trunc_off = gen;  // first draw offset not consumed by this batch
         bool target_hit = false;
         bool rebuild = false;  // BAND: a committed flip put a node outside S into b_nodes
-        const int cut0 = cut, nb0 = nb, rem0 = rem;
-        const int64_t steps0 = steps;
+        const int cut0 = cut, nb0 = nb;
+        const int64_t steps0 = FULL ? steps_in + ((int)p.n_steps - rem) : 0;  // yield index at the batch's start
         const int last_flip0 = last_flip;
         const int a_last0 = FULL && last_flip0 >= 0 ? (int)a[last_flip0] : 0;
         int cut_after = 0, nb_after = 0;
@@ -1023,7 +1052,6 @@ __global__ __launch_bounds__(256, (RMAX == 8 ? 4 : 1)) void flip2_kernel(KParams
             FC_PROF(30, t_ap2 - t_ap1);
         }
         compiler_fence();  // (the marks: cleared by each segment pass)
-        steps = steps0 + (rem0 - rem);
         FC_STAMP(t_d);
         FC_PROF(3, t_d - t_c);
 
@@ -1032,7 +1060,6 @@ __global__ __launch_bounds__(256, (RMAX == 8 ? 4 : 1)) void flip2_kernel(KParams
         const bool done = lane < end;
         const bool is_acc = (st & ST_AC) != 0;
         const bool proposed = (st & LF_HIT) && done;
-        n_prop += __popcll(__ballot(proposed));
         n_acc += __popcll(__ballot(is_acc));
         n_ic += __popcll(__ballot((st & ST_IC) != 0));
         n_ip += __popcll(__ballot((st & ST_IP) != 0));
@@ -1056,21 +1083,24 @@ __global__ __launch_bounds__(256, (RMAX == 8 ? 4 : 1)) void flip2_kernel(KParams
             }
             my_wait = geom_from(u53(g.x0, g.x1), p.log1mp[nb_after]);
         }
-        // (run_len is 0 off the accepting lanes: no guard, no exec-mask branch)
-        {
+        // With the queue on, every accepted state's terms of the sums are formed by wait_flush
+        // from its queue entry (|cut|, |B|, run length), and the start state's run joins the
+        // queued current state's (below); only a start state that is not queued is summed here.
+        if (!defer) {
+            // (run_len is 0 off the accepting lanes: no guard, no exec-mask branch)
             const int cr = cut_after * run_len, br = nb_after * run_len;  // < 2^31: |cut| < 2^24, runs <= 64
             acc_cut += cr;
             acc_cut2 += (int64_t)cr * cut_after;
             acc_nb += br;
             acc_nb2 += (int64_t)br * nb_after;
+            acc_wait += my_wait * run_len;
         }
-        if (!defer) acc_wait += my_wait * run_len;
-        if (lane == 0 && r0) {
+        if (lane == 0 && r0 && (!defer || qn == 0)) {
             acc_cut += (int64_t)cut0 * r0;
             acc_cut2 += (int64_t)cut0 * cut0 * r0;
             acc_nb += (int64_t)nb0 * r0;
             acc_nb2 += (int64_t)nb0 * nb0 * r0;
-            if (!defer || qn == 0) acc_wait += wait_cur * r0;  // else: the queued current state's run
+            acc_wait += wait_cur * r0;  // (queued: the current state's run takes r0)
         }
         const int64_t t_acc = FULL ? steps0 + __popcll(VSM & bits_below(ln + 1)) : 0;  // yield index of this lane
         if constexpr (FULL) {
@@ -1100,9 +1130,9 @@ __global__ __launch_bounds__(256, (RMAX == 8 ? 4 : 1)) void flip2_kernel(KParams
                     q_d[qi] = d;
                     q_nb[qi] = (uint32_t)nb_after;
                     q_run[qi] = (uint32_t)run_len;
+                    q_c[qi] = (uint32_t)cut_after | ((uint32_t)(1 - av) << 31);
                     if constexpr (FULL) {
                         q_v[qi] = (uint32_t)v | ((inA & nbr) << 16);
-                        q_c[qi] = (uint32_t)cut_after | ((uint32_t)(1 - av) << 31);
                         if (qi == 0) misc[2] = (uint64_t)t_acc;
                     }
                 }
@@ -1251,12 +1281,15 @@ __global__ __launch_bounds__(256, (RMAX == 8 ? 4 : 1)) void flip2_kernel(KParams
         }
         if (BAND && lane < p.words) p.sbits[(size_t)c * p.words + lane] = sb[lane];
     }
-    const int64_t cnt_prop = n_prop, cnt_acc = n_acc, cnt_ic = n_ic, cnt_ip = n_ip;  // already wave totals
+    cnt_fold();
+    const int taken = (int)p.n_steps - rem;  // steps taken (fewer than n_steps: the launch ended stuck)
+    const int64_t cnt_acc = rl64(cnt64, 0), cnt_ic = rl64(cnt64, 1), cnt_ip = rl64(cnt64, 2);
+    const int64_t cnt_prop = (int64_t)taken + cnt_ic + cnt_ip;
     wave_sum64_all(acc_cut, acc_nb, acc_wait, acc_cut2, acc_nb2);
     if (FULL && p.tl_len && lane == 0) p.tl_len[c] = (int64_t)misc[3];
     if (lane == 0) {
         scp->draw = draw;
-        scp->steps = steps;
+        scp->steps = steps_in + taken;
         scp->proposals += cnt_prop;
         scp->accepted += cnt_acc;
         scp->inv_contig += cnt_ic;

@@ -1,6 +1,7 @@
 // Internal structures shared by the host graph builder, the C-ABI layer and the kernels.
 #pragma once
 
+#include <stddef.h>
 #include <stdint.h>
 
 #include <string>
@@ -92,7 +93,11 @@ struct KParams {
     uint32_t lemire_thresh;     // 2^32 mod n
     uint32_t chain_id_offset;
     uint32_t seed_lo, seed_hi;
-    int32_t pop_lo, pop_hi;     // (unused by the kernels: each chain's bounds are in ChainScalars)
+    int32_t pop_lo;             // (unused by the kernels: each chain's bounds are in ChainScalars)
+    // k = 2: [kPhiloxKeyWords] the seed's Philox round keys (fc_philox.h).  It takes the word of
+    // the former pop_hi (as unused as pop_lo) and the padding before n_steps, so every other
+    // field keeps its offset and the other kernels' code is unchanged
+    const uint32_t *pkeys;
     int64_t n_steps;            // steps to advance per chain in this launch
     int64_t max_draws;          // per chain per launch
     int8_t *assign;             // [n_chains * n]
@@ -172,6 +177,7 @@ struct KParams {
     int32_t band_step0;         // largest power of two below `words` (rank search over the words)
     uint64_t *sbits;            // [n_chains * words]
 };
+static_assert(offsetof(KParams, pkeys) == 64 && offsetof(KParams, n_steps) == 72, "KParams: pkeys fills pop_hi's slot");
 
 // chain dealing: SIMD keys are XCC_ID[2:0] . HW_ID[15:4] (SIMD, pipe, CU, SH, SE)
 constexpr int kDealKeys = 1 << 15;

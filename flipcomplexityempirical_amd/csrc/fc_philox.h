@@ -49,6 +49,41 @@ FC_HD Words4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, u
     return Words4{c0, c1, c2, c3};
 }
 
+// The k = 2 flip kernel's form: the ten rounds' key words (kPhiloxKeyWords: k0, k1 of round 0,
+// of round 1, ...) come from memory, filled once per run by the host (philox_round_keys), and are
+// read by scalar loads where the words are needed, instead of two scalar adds per round in every
+// call.  The same function of (counter, seed) as philox4x32_10.
+constexpr int kPhiloxKeyWords = 20;
+inline void philox_round_keys(uint32_t k0, uint32_t k1, uint32_t *out) {
+    for (int r = 0; r < 10; ++r) {
+        out[2 * r] = k0 + (uint32_t)r * 0x9E3779B9u;
+        out[2 * r + 1] = k1 + (uint32_t)r * 0xBB67AE85u;
+    }
+}
+#if defined(__HIPCC__) || defined(__HIP__)
+typedef const uint32_t __attribute__((address_space(4))) *PhiloxKeys;  // constant memory: scalar loads
+__device__ __forceinline__ Words4 philox4x32_10_keys(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, PhiloxKeys kp) {
+    uint32_t K[kPhiloxKeyWords];
+#pragma unroll
+    for (int i = 0; i < kPhiloxKeyWords; ++i) K[i] = kp[i];
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+#if defined(__HIP_DEVICE_COMPILE__)
+        const uint32_t n0 = __builtin_amdgcn_bitop3_b32((uint32_t)(p1 >> 32), c1, K[2 * r], 0x96);  // 3-way xor
+        const uint32_t n2 = __builtin_amdgcn_bitop3_b32((uint32_t)(p0 >> 32), c3, K[2 * r + 1], 0x96);
+#else
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ K[2 * r], n2 = (uint32_t)(p0 >> 32) ^ c3 ^ K[2 * r + 1];
+#endif
+        c0 = n0;
+        c1 = (uint32_t)p1;
+        c2 = n2;
+        c3 = (uint32_t)p0;
+    }
+    return Words4{c0, c1, c2, c3};
+}
+#endif
+
 // 53-bit mantissa of CPython random() / numpy random_sample() from two words.
 FC_HD uint64_t mant53(uint32_t a, uint32_t b) { return ((uint64_t)(a >> 5) << 26) | (uint64_t)(b >> 6); }
 

@@ -108,6 +108,7 @@ struct fc_run : fc::RunShape {
     DevBuf<fc::ChainScalars> d_sc;
     DevBuf<uint64_t> d_thresh;
     DevBuf<double> d_log1mp;
+    DevBuf<uint32_t> d_pkeys;  // the seed's Philox round keys (k = 2 flip kernel)
     DevBuf<int32_t> d_labels;
     DevBuf<int64_t> d_cut_hist, d_nb_hist;
     DevBuf<int64_t> d_edge_acc;

@@ -1,0 +1,163 @@
+#!/usr/bin/env python3
+"""Static instruction mix of a kernel's main loop, from a device assembly listing
+(hipcc --cuda-device-only -S).  For the named kernel instance it prints the resource figures,
+the instruction totals by class of its largest outermost loop (the batch loop of flip2_kernel)
+and of every loop nested in it, and, in a listing of the phase-profile build (FC_LIB_VARIANT=prof),
+the totals of the regions between the stamps, in listing order (the block layout follows the
+source order only roughly: read those as a guide).
+
+Instructions are classed by prefix alone; most of the loop runs about once per batch, so the
+static totals are a usable proxy for the dynamic ones (SQ_INSTS_* of tools/pmc_lds.sh confirm).
+
+Usage: python3 tools/loop_mix.py LISTING.s 'flip2_kernel<8, 4, false, false, false, false>'
+           [--remarks FILE]   the compile's -Rpass-analysis=kernel-resource-usage output (adds spills)
+           [--marker REGEX]   the instruction that separates regions (default: the stamps' clock read)
+"""
+import argparse
+import os
+import re
+import subprocess
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import kres  # noqa: E402
+
+CLASSES = ["VALU", "SALU", "SMEM", "LDS", "VMEM", "branch", "wait/nop", "other"]
+# first match wins
+PREFIXES = [("s_cbranch", "branch"), ("s_branch", "branch"), ("s_setpc", "branch"), ("s_swappc", "branch"),
+            ("s_call", "branch"), ("s_endpgm", "branch"),
+            ("s_waitcnt", "wait/nop"), ("s_nop", "wait/nop"), ("s_sleep", "wait/nop"),
+            ("s_load", "SMEM"), ("s_buffer_load", "SMEM"), ("s_memtime", "SMEM"), ("s_memrealtime", "SMEM"),
+            ("s_", "SALU"), ("v_", "VALU"), ("ds_", "LDS"),
+            ("global_", "VMEM"), ("flat_", "VMEM"), ("buffer_", "VMEM"), ("scratch_", "VMEM")]
+
+
+def classify(mn):
+    for pre, cls in PREFIXES:
+        if mn.startswith(pre):
+            return cls
+    return "other"
+
+
+def demangle(names):
+    out = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True).stdout.splitlines()
+    return dict(zip(names, out))
+
+
+def kernel_body(lines, flt):
+    """(mangled name, demangled name, body lines, info lines) of the one kernel matching flt."""
+    starts = [(i, m.group(1)) for i, l in enumerate(lines) if (m := re.match(r"^(_Z\w+):\s", l))]
+    dm = demangle([n for _, n in starts])
+    hits = [(i, n) for i, n in starts if flt in dm[n]]
+    if len(hits) != 1:
+        sys.exit(f"{len(hits)} kernels match {flt!r}:\n" + "\n".join(dm[n] for _, n in hits[:40]))
+    i0, name = hits[0]
+    i1 = next(i for i in range(i0, len(lines)) if ".end_amdhsa_kernel" in lines[i] or lines[i].startswith(".Lfunc_end"))
+    k = next((i for i in range(i1, min(i1 + 80, len(lines))) if lines[i].startswith("; Kernel info")), None)
+    info = []
+    if k is not None:
+        for l in lines[k + 1:k + 40]:
+            if not l.startswith(";"):
+                break
+            info.append(l[1:].strip())
+    return name, dm[name], lines[i0 + 1:i1], info
+
+
+def parse_blocks(body):
+    """Blocks in listing order: {"label", "loops": headers of the enclosing loops, outermost first,
+    "insts": mnemonics}.  The loop nest is read from the compiler's block comments."""
+    blocks, cur, pending = [], None, None
+    for l in body:
+        m = re.match(r"^(?:\.L(BB\d+_\d+):|; %bb\.(\d+):)(.*)", l)
+        if m:
+            cur = {"label": m.group(1) or f"bb.{m.group(2)}", "loops": [], "insts": [], "self": False}
+            blocks.append(cur)
+            pending = cur
+            l = ";" + m.group(3)
+        s = l.strip()
+        if s.startswith(";"):
+            if pending is not None:
+                for h, d in re.findall(r"(?:Parent Loop|in Loop: Header=)\s*(BB\d+_\d+) Depth[= ](\d+)", s):
+                    pending["loops"].append((int(d), h))
+                if re.search(r"This (Inner )?Loop Header: Depth=(\d+)", s):
+                    d = int(re.search(r"Header: Depth=(\d+)", s).group(1))
+                    pending["loops"].append((d, pending["label"]))
+            continue
+        if not s or s.startswith("."):
+            continue
+        pending = None
+        if cur is not None:
+            cur["insts"].append(s.split()[0])
+    for b in blocks:
+        b["loops"] = [h for _, h in sorted(set(b["loops"]))]
+    # "in Loop: Header=H Depth=d" names only the innermost loop: complete the chain from H's own
+    chain = {b["label"]: b["loops"] for b in blocks if b["loops"] and b["loops"][-1] == b["label"]}
+    for b in blocks:
+        if b["loops"] and b["loops"][-1] in chain:
+            b["loops"] = chain[b["loops"][-1]]
+    return blocks
+
+
+def mix(insts):
+    t = dict.fromkeys(CLASSES, 0)
+    for mn in insts:
+        t[classify(mn)] += 1
+    return t
+
+
+def row(label, t):
+    return f"{label:<28}" + "".join(f"{t[c]:>9}" for c in CLASSES) + f"{sum(t.values()):>9}"
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("listing")
+    ap.add_argument("kernel")
+    ap.add_argument("--remarks")
+    ap.add_argument("--marker", default=r"^s_memtime")
+    args = ap.parse_args()
+    with open(args.listing) as fh:
+        lines = fh.read().splitlines()
+    name, pretty, body, info = kernel_body(lines, args.kernel)
+    print(pretty)
+    keep = ("codeLenInByte", "TotalNumSgprs", "NumVgprs", "NumAgprs", "ScratchSize", "Occupancy")
+    print("  " + "  ".join(i.replace(" = ", ": ") for i in info if i.startswith(keep)))
+    if args.remarks:
+        with open(args.remarks) as fh:
+            for r in kres.parse_remarks(fh.read()):
+                if r["name"].startswith(pretty.split("(")[0]):
+                    print("  " + kres.format_row(r))
+    blocks = parse_blocks(body)
+    top = {}
+    for b in blocks:
+        if b["loops"]:
+            top[b["loops"][0]] = top.get(b["loops"][0], 0) + len(b["insts"])
+    if not top:
+        sys.exit("no loop in this kernel")
+    main_loop = max(top, key=top.get)
+    inl = [b for b in blocks if b["loops"] and b["loops"][0] == main_loop]
+    print(f"\nmain loop {main_loop}: {len(inl)} blocks (static instructions)")
+    print(f"{'':<28}" + "".join(f"{c:>9}" for c in CLASSES) + f"{'total':>9}")
+    print(row("whole loop", mix([m for b in inl for m in b["insts"]])))
+    own = [m for b in inl if len(b["loops"]) == 1 for m in b["insts"]]
+    print(row("  outside nested loops", mix(own)))
+    nested = []
+    for b in inl:
+        for d, h in enumerate(b["loops"][1:], 2):
+            if (d, h) not in nested:
+                nested.append((d, h))
+    for d, h in nested:
+        sub = [m for b in inl if len(b["loops"]) >= d and b["loops"][d - 1] == h for m in b["insts"]]
+        print(row("  " * (d - 1) + f"loop {h} (depth {d})", mix(sub)))
+    mk = re.compile(args.marker)
+    seq = [m for b in inl for m in b["insts"]]
+    cuts = [i for i, m in enumerate(seq) if mk.search(m)]
+    if cuts:
+        print(f"\nregions between the {len(cuts)} markers, in listing order")
+        edges = [0] + cuts + [len(seq)]
+        for r in range(len(edges) - 1):
+            print(row(f"  region {r}", mix(seq[edges[r]:edges[r + 1]])))
+
+
+if __name__ == "__main__":
+    main()
