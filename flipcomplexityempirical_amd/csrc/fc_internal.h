@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/flipchain.h"
+#include "fc_replay.h"
 
 namespace fc {
 
@@ -234,42 +235,41 @@ int launch_deal_order(const uint32_t *ctime, const ChainScalars *sc, int n, int 
                       uint32_t *order, uint32_t *deal, void *stream);
 
 // Series diagnostics (fc_series.hip): expand the event logs of chains [c0, c0 + nc) into
-// dense |cut| series x[(c - c0) * stride + t], t < len[c], then accumulate per lag
-// P = sum x_t x_{t+L}, H = sum_{t < len-L} x_t, G = sum_{t >= L} x_t into sums[c][lag][3].
+// dense |cut| series x[cl * stride + t], t < len[cl], then accumulate per lag
+// P = sum x_t x_{t+L}, H = sum_{t < len-L} x_t, G = sum_{t >= L} x_t into sums[c0 + cl][lag][3].
+// ev_len, t0, cut0 and len are the call's: [nc], indexed by cl (fc_replay.h).
 int launch_series_expand(const fc_event *events, int64_t ev_cap, const int64_t *ev_len, const int64_t *t0,
                          const int32_t *cut0, const int64_t *len, int32_t c0, int32_t nc, int64_t stride,
                          int64_t max_len, uint16_t *x, void *stream);
 int launch_series_lagsums(const uint16_t *x, const int64_t *len, int32_t c0, int32_t nc, int64_t stride,
                           int64_t max_len, const int32_t *lags, int32_t nlags, unsigned long long *sums,
                           void *stream);
-// Frame-edge slope / angle series of chains [c0, c0 + nc), k = 2 (fc_series.hip): entry 0 is
-// the window start (assignment a0), entry i + 1 the state after event i.  tog_idx[node] is the
-// node's row in tog_mask[.][4] (frame edges incident to it) or -1.  n_frame <= 256.
-int launch_frame_series(const int8_t *a0, int32_t npad, const fc_event *events, int64_t ev_cap,
-                        const int64_t *ev_len, int32_t c0, int32_t nc, int32_t n_frame, const int32_t *fu,
-                        const int32_t *fv, const double *mid, double cx, double cy, const int32_t *tog_idx,
-                        const uint64_t *tog_mask, int32_t n_rows, int32_t n_nodes, int64_t cap, double *slope,
-                        double *angle, int32_t *cnt, void *stream);
-// Change points of the same series (fc_run_frame_series_changes): cp_off == nullptr counts them
-// per chain into cp_cnt[cl]; otherwise writes (t, slope, angle) at cp_off[cl].  n_rows: rows of
-// tog_mask, n_nodes: entries of tog_idx (the tables are staged in LDS when they fit).
-int launch_frame_changes(const int8_t *a0, int32_t npad, const fc_event *events, int64_t ev_cap,
-                         const int64_t *ev_len, int32_t c0, int32_t nc, int32_t n_frame, const int32_t *fu,
-                         const int32_t *fv, const double *mid, double cx, double cy, const int32_t *tog_idx,
-                         const uint64_t *tog_mask, int32_t n_rows, int32_t n_nodes, const int64_t *t0,
-                         int64_t *cp_cnt, const int64_t *cp_off, int64_t *t_out, double *slope, double *angle,
-                         int64_t *wcnt, void *stream);
-constexpr int kFrameWaves = 4;  // waves per chain of the frame-series kernels (wcnt: [nc][kFrameWaves])
-// One-pass form of the above (count and write together): each chain's waves stage their change
-// points at st_* + cl * stage_cap + w * (stage_cap / kFrameWaves), counts in wcnt / cp_cnt; then
-// launch_frame_compact packs them at cp_off.  stage_cap / kFrameWaves must exceed the events of any
-// wave's range: 64 * ceil(ceil(ev_cap / 64) / kFrameWaves) + 1.
-int launch_frame_stage(const int8_t *a0, int32_t npad, const fc_event *events, int64_t ev_cap,
-                       const int64_t *ev_len, int32_t c0, int32_t nc, int32_t n_frame, const int32_t *fu,
-                       const int32_t *fv, const double *mid, double cx, double cy, const int32_t *tog_idx,
-                       const uint64_t *tog_mask, int32_t n_rows, int32_t n_nodes, const int64_t *t0,
-                       int64_t *cp_cnt, int64_t stage_cap, int64_t *st_t, double *st_s, double *st_a,
-                       int64_t *wcnt, void *stream);
+
+// Frame-edge slope / angle series of the window's chains, k = 2 (fc_series.hip): entry 0 is the
+// window start (assignment a0), entry i + 1 the state after event i.
+constexpr int kFrameWaves = 4;  // waves per chain of the frame-series kernel (wcnt: [nc][kFrameWaves])
+// The kernel's MODE (described at frame_series_kernel).  kFrameStage's cap / kFrameWaves must exceed
+// the events of any wave's range: 64 * ceil(ceil(ev_cap / 64) / kFrameWaves) + 1
+enum FrameMode { kFrameEvents = 0, kFrameCount = 1, kFrameWrite = 2, kFrameStage = 3 };
+struct FrameParams {
+    LogWindow log;             // t_end is not read
+    int32_t n_frame;           // frame edges, at most 256
+    const int32_t *fu, *fv;    // [n_frame] their ends
+    const double *mid;         // [2 n_frame] their midpoints
+    double cx, cy;             // the angle's centre
+    const int32_t *tog_idx;    // [n] the node's row in tog_mask, or -1
+    const uint64_t *tog_mask;  // [n_rows][4] the frame edges incident to the node
+    int32_t n_rows;            // (the tables are staged in LDS when they fit)
+    // outputs; a mode leaves those it does not name alone
+    int64_t cap;               // kFrameEvents: entries per chain; kFrameStage: staged entries per chain
+    double *slope, *angle;     // kFrameEvents: [nc * cap]; kFrameWrite: flat; kFrameStage: [nc * cap]
+    int32_t *n_cut;            // kFrameEvents: [nc * cap] frame edges cut
+    int64_t *t_out;            // kFrameWrite, kFrameStage: the yield each change point starts at
+    int64_t *cp_cnt;           // kFrameCount, kFrameStage: [nc]
+    const int64_t *cp_off;     // kFrameWrite: [nc]
+    int64_t *wcnt;             // all but kFrameEvents: [nc][kFrameWaves]
+};
+int launch_frame(const FrameParams &p, int mode, void *stream);
 int launch_frame_compact(int32_t nc, int64_t stage_cap, const int64_t *st_t, const double *st_s,
                          const double *st_a, const int64_t *wcnt, const int64_t *cp_off, int64_t *t_out,
                          double *slope, double *angle, void *stream);

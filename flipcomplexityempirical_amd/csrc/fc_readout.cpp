@@ -2,6 +2,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -14,6 +15,103 @@ int check_event_overflow(const fc_run *r, const char *who, int32_t chain, const 
     if (s.ev_len > r->ev_cap)
         return fail(FC_ERR_ARG, std::string(who) + ": chain " + std::to_string(chain) +
                                     " overflowed event_cap; reset the series window more often");
+    return FC_OK;
+}
+
+// ---- the driver the series calls share (DESIGN.md §4 "Series window") -------------------------
+
+struct CallRules {
+    const char *flip_pass = nullptr;  // the pass replays flips, which a ReCom run does not log: its name
+    const char *unset = nullptr;      // the setter the pass needs and the run has not had, or null
+    const char *k2_only = nullptr;    // the pass follows k = 2 flips: what to say of another run
+};
+
+// The checks every series call `who` over chains [c0, c0 + nc) makes of the run and the range,
+// before any device work.
+int check_series_call(const fc_run *r, const char *who, int32_t c0, int32_t nc, const CallRules &rules) {
+    const std::string w(who);
+    if (rules.flip_pass && r->p.proposal == FC_PROPOSE_RECOM)
+        return fail(FC_ERR_UNSUPPORTED, w + ": " + rules.flip_pass + " replays the flip log (not ReCom)");
+    if (!r->d_events) return fail(FC_ERR_ARG, w + ": FC_DIAG_SERIES not enabled");
+    if (rules.unset) return fail(FC_ERR_ARG, w + ": call " + rules.unset + " first");
+    if (rules.k2_only && r->p.k != 2) return fail(FC_ERR_UNSUPPORTED, w + ": " + rules.k2_only);
+    if (c0 < 0 || nc < 0 || c0 + nc > r->n_chains) return fail(FC_ERR_ARG, w + ": chain range");
+    return FC_OK;
+}
+
+struct SeriesCall {
+    fc::LogWindow log{};
+    std::vector<fc::ChainScalars> sc;  // the scalars of chains [c0, c0 + nc)
+};
+
+// The window of a checked call: the chains' scalars, the per-chain overflow check (and, with
+// bound_yields, a window below 2^30 yields), and ev_len, t0, t_end, indexed by the call-local
+// chain, in r->d_ser_meta.  download_scalars leaves the run idle, so the upload is a blocking copy
+// of pageable memory: the window is on the device when this returns.
+int open_window(fc_run *r, const char *who, int32_t c0, int32_t nc, bool bound_yields, SeriesCall &s) {
+    const std::string w(who);
+    s.log = fc::LogWindow{};
+    s.log.a0 = r->d_ser_a0;
+    s.log.npad = r->npad;
+    s.log.n = r->g.n;
+    s.log.k = r->p.k;
+    s.log.events = r->d_events;
+    s.log.ev_cap = r->ev_cap;
+    s.log.c0 = c0;
+    s.log.nc = nc;
+    if (int rc = download_scalars(r, c0, nc, s.sc)) return rc;
+    std::vector<int64_t> meta((size_t)3 * nc);
+    for (int32_t i = 0; i < nc; ++i) {
+        const fc::ChainScalars &x = s.sc[i];
+        if (int rc = check_event_overflow(r, who, c0 + i, x)) return rc;
+        if (bound_yields && x.steps - x.ser_t0 + 1 >= (int64_t(1) << 30))
+            return fail(FC_ERR_ARG, w + ": chain " + std::to_string(c0 + i) +
+                                        "'s window has 2^30 yields or more; reset the series window more often");
+        meta[i] = x.ev_len;
+        meta[(size_t)nc + i] = x.ser_t0;
+        meta[(size_t)2 * nc + i] = x.steps + 1;
+    }
+    if (int rc = r->d_ser_meta.grow(meta.size())) return rc;
+    HIP_TRY(hipMemcpy(r->d_ser_meta, meta.data(), meta.size() * 8, hipMemcpyHostToDevice));
+    s.log.ev_len = r->d_ser_meta;
+    s.log.t0 = r->d_ser_meta + nc;
+    s.log.t_end = r->d_ser_meta + 2 * (size_t)nc;
+    return FC_OK;
+}
+
+// The int64 outputs of a series call, one after the other in r->d_ser_out.
+struct OutPack {
+    std::vector<size_t> off;  // [outputs + 1]
+    int64_t *dev = nullptr;
+
+    int reserve(fc_run *r, std::initializer_list<size_t> sizes) {
+        off.assign(1, 0);
+        for (size_t sz : sizes) off.push_back(off.back() + sz);
+        if (int rc = r->d_ser_out.grow(off.back())) return rc;
+        dev = r->d_ser_out;
+        return FC_OK;
+    }
+    int64_t *at(size_t i) const { return dev + off[i]; }
+    // the outputs the caller asked for (a host pointer, a size), then the stream synchronised
+    int fetch(fc_run *r, std::initializer_list<int64_t *> host) const {
+        size_t i = 0;
+        for (int64_t *h : host) {
+            if (h && off[i + 1] > off[i])
+                HIP_TRY(hipMemcpyAsync(h, at(i), (off[i + 1] - off[i]) * 8, hipMemcpyDeviceToHost, r->stream));
+            ++i;
+        }
+        HIP_TRY(hipStreamSynchronize(r->stream));
+        return FC_OK;
+    }
+};
+
+// histogram edges as fc_run_set_elections / fc_run_set_shapes take them
+int check_hist_edges(const char *who, const char *name, int32_t n, int32_t max, const int64_t *edges) {
+    const std::string w(who);
+    if (n < 0 || n > max) return fail(FC_ERR_ARG, w + ": n_" + name + " must be 0.." + std::to_string(max));
+    if (n > 0 && !edges) return fail(FC_ERR_ARG, w + ": null " + name);
+    for (int32_t i = 1; i < n; ++i)
+        if (edges[i] <= edges[i - 1]) return fail(FC_ERR_ARG, w + ": " + name + " must be strictly ascending");
     return FC_OK;
 }
 
@@ -40,6 +138,48 @@ void build_toggles(int32_t n, int32_t n_frame, const int32_t *frame_u, const int
             tog[(size_t)tog_idx[x] * 4 + (j >> 6)] |= uint64_t(1) << (j & 63);
         }
     }
+}
+
+// The inputs of a frame launch over `log`.  The frame tables are kept by the run and uploaded
+// when the frame differs from the last call's (either frame entry point's).
+int frame_inputs(fc_run *r, const fc::LogWindow &log, int32_t n_frame, const int32_t *frame_u,
+                 const int32_t *frame_v, const double *mid_xy, double cx, double cy, fc::FrameParams &fp) {
+    const int32_t n = r->g.n;
+    uint64_t h = fnv1a(fc::kFnvBasis, &n_frame, sizeof n_frame);
+    h = fnv1a(h, frame_u, (size_t)n_frame * 4);
+    h = fnv1a(h, frame_v, (size_t)n_frame * 4);
+    h = fnv1a(h, mid_xy, (size_t)n_frame * 16);
+    if (!r->d_fc_fuv || h != r->fc_frame_hash) {
+        std::vector<int32_t> tog_idx;
+        std::vector<uint64_t> tog;
+        build_toggles(n, n_frame, frame_u, frame_v, tog_idx, tog);
+        int q;
+        if ((q = r->d_fc_fuv.alloc((size_t)2 * 256))) return q;
+        if ((q = r->d_fc_tidx.alloc((size_t)n))) return q;
+        if ((q = r->d_fc_tog.alloc((size_t)4 * 512))) return q;
+        if ((q = r->d_fc_mid.alloc((size_t)2 * 256))) return q;
+        if (n_frame) {
+            HIP_TRY(hipMemcpy(r->d_fc_fuv, frame_u, (size_t)n_frame * 4, hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(r->d_fc_fuv + n_frame, frame_v, (size_t)n_frame * 4, hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(r->d_fc_mid, mid_xy, (size_t)n_frame * 16, hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(r->d_fc_tog, tog.data(), tog.size() * 8, hipMemcpyHostToDevice));
+        }
+        HIP_TRY(hipMemcpy(r->d_fc_tidx, tog_idx.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+        r->fc_frame_hash = h;
+        r->fc_rows = (int32_t)(tog.size() / 4);
+    }
+    fp = fc::FrameParams{};
+    fp.log = log;
+    fp.n_frame = n_frame;
+    fp.fu = r->d_fc_fuv;
+    fp.fv = r->d_fc_fuv + n_frame;
+    fp.mid = r->d_fc_mid;
+    fp.cx = cx;
+    fp.cy = cy;
+    fp.tog_idx = r->d_fc_tidx;
+    fp.tog_mask = r->d_fc_tog;
+    fp.n_rows = r->fc_rows;
+    return FC_OK;
 }
 
 }  // namespace
@@ -180,21 +320,19 @@ int fc_run_series_reset(fc_run *r) {
 
 int fc_run_autocorr(fc_run *r, const int32_t *lags, int32_t nlags, int64_t *lag_sums, double *acf) {
     if (!r || !lags || nlags <= 0 || !lag_sums) return fail(FC_ERR_ARG, "fc_run_autocorr: null argument");
-    if (!r->d_events) return fail(FC_ERR_ARG, "fc_run_autocorr: FC_DIAG_SERIES not enabled");
+    const int32_t C = r->n_chains;
+    if (int rc = check_series_call(r, "fc_run_autocorr", 0, C, {})) return rc;
     for (int32_t j = 0; j < nlags; ++j)
         if (lags[j] < 0) return fail(FC_ERR_ARG, "fc_run_autocorr: negative lag");
-    const int32_t C = r->n_chains;
-    std::vector<fc::ChainScalars> sc;
-    if (int rc = download_scalars(r, 0, C, sc)) return rc;
-    std::vector<int64_t> ev_len(C), t0(C), len(C);
+    SeriesCall s;
+    if (int rc = open_window(r, "fc_run_autocorr", 0, C, false, s)) return rc;
+    const fc::LogWindow &w = s.log;
+    std::vector<int64_t> len(C);
     std::vector<int32_t> cut0(C);
     int64_t max_len = 0;
     for (int32_t c = 0; c < C; ++c) {
-        if (int rc = check_event_overflow(r, "fc_run_autocorr", c, sc[c])) return rc;
-        ev_len[c] = sc[c].ev_len;
-        t0[c] = sc[c].ser_t0;
-        cut0[c] = sc[c].ser_cut0;
-        len[c] = sc[c].steps - sc[c].ser_t0 + 1;  // yields t0 .. steps
+        cut0[c] = s.sc[c].ser_cut0;
+        len[c] = s.sc[c].steps - s.sc[c].ser_t0 + 1;  // yields t0 .. steps
         max_len = std::max(max_len, len[c]);
     }
     // lag 0 is always evaluated first: it yields the window totals Sx = H_0 and Sxx = P_0
@@ -205,28 +343,25 @@ int fc_run_autocorr(fc_run *r, const int32_t *lags, int32_t nlags, int64_t *lag_
     // device scratch: metadata + dense series for a batch of chains (<= 1 GiB)
     const int64_t stride = (max_len + 7) & ~int64_t(7);
     const int32_t batch = (int32_t)std::max<int64_t>(1, std::min<int64_t>({C, 65535, (int64_t(1) << 29) / stride}));
-    DevBuf<int64_t> d_meta;  // ev_len, t0, len: [C] each
+    DevBuf<int64_t> d_len;
     DevBuf<int32_t> d_cut0, d_lags;
     DevBuf<uint16_t> d_x;
     DevBuf<unsigned long long> d_sums;
     int q;
-    if ((q = d_meta.alloc((size_t)3 * C))) return q;
-    if ((q = d_cut0.alloc((size_t)C))) return q;
-    if ((q = d_lags.alloc((size_t)nl))) return q;
+    if ((q = d_len.upload(len))) return q;
+    if ((q = d_cut0.upload(cut0))) return q;
+    if ((q = d_lags.upload(lg))) return q;
     if ((q = d_x.alloc((size_t)batch * stride))) return q;
     if ((q = d_sums.alloc((size_t)C * nl * 3))) return q;
-    HIP_TRY(hipMemcpy(d_meta, ev_len.data(), (size_t)C * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_meta + C, t0.data(), (size_t)C * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_meta + 2 * C, len.data(), (size_t)C * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_cut0, cut0.data(), (size_t)C * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_lags, lg.data(), (size_t)nl * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemsetAsync(d_sums, 0, (size_t)C * nl * 3 * 8, r->stream));
     for (int32_t c0 = 0; c0 < C; c0 += batch) {
+        // the window's per-chain arrays from the batch's first chain on: the kernels index them
+        // by the chain within the batch
         const int32_t nc = std::min(batch, C - c0);
-        int e = fc::launch_series_expand(r->d_events, r->ev_cap, d_meta, d_meta + C, d_cut0, d_meta + 2 * C, c0,
+        int e = fc::launch_series_expand(w.events, w.ev_cap, w.ev_len + c0, w.t0 + c0, d_cut0 + c0, d_len + c0, c0,
                                          nc, stride, max_len, d_x, r->stream);
         if (e) return fail(FC_ERR_HIP, std::string("series expand: ") + hipGetErrorString((hipError_t)e));
-        e = fc::launch_series_lagsums(d_x, d_meta + 2 * C, c0, nc, stride, max_len, d_lags, nl, d_sums,
+        e = fc::launch_series_lagsums(d_x, d_len + c0, c0, nc, stride, max_len, d_lags, nl, d_sums,
                                       r->stream);
         if (e) return fail(FC_ERR_HIP, std::string("series lag sums: ") + hipGetErrorString((hipError_t)e));
     }
@@ -259,56 +394,35 @@ int fc_run_frame_series(fc_run *r, int32_t c0, int32_t nc, int32_t n_frame, cons
                         double *slope, double *angle, int32_t *n_cut, int64_t *len) {
     if (!r || !frame_u || !frame_v || !mid_xy || !slope || !angle || !n_cut || !len)
         return fail(FC_ERR_ARG, "fc_run_frame_series: null argument");
-    if (!r->d_events) return fail(FC_ERR_ARG, "fc_run_frame_series: FC_DIAG_SERIES not enabled");
-    if (r->p.k != 2)
-        return fail(FC_ERR_UNSUPPORTED, "fc_run_frame_series: the frame series follows k = 2 flips (the reference "
-                                        "computes boundary_slope only in its two-district drivers)");
-    if (c0 < 0 || nc < 0 || c0 + nc > r->n_chains) return fail(FC_ERR_ARG, "fc_run_frame_series: chain range");
+    CallRules rules;
+    rules.k2_only = "the frame series follows k = 2 flips (the reference computes boundary_slope only in its "
+                    "two-district drivers)";
+    if (int rc = check_series_call(r, "fc_run_frame_series", c0, nc, rules)) return rc;
     if (n_frame < 0 || n_frame > 256) return fail(FC_ERR_UNSUPPORTED, "fc_run_frame_series: at most 256 frame edges");
     const int32_t n = r->g.n;
     if (int rc = check_frame_edges("fc_run_frame_series", n, n_frame, frame_u, frame_v)) return rc;
-    std::vector<int32_t> tog_idx;
-    std::vector<uint64_t> tog;
-    build_toggles(n, n_frame, frame_u, frame_v, tog_idx, tog);
     if (nc == 0) return FC_OK;
-    std::vector<fc::ChainScalars> sc;
-    if (int rc = download_scalars(r, c0, nc, sc)) return rc;
-    std::vector<int64_t> ev_len(r->n_chains, 0);
+    SeriesCall s;
+    if (int rc = open_window(r, "fc_run_frame_series", c0, nc, false, s)) return rc;
     for (int32_t i = 0; i < nc; ++i) {
-        if (int rc = check_event_overflow(r, "fc_run_frame_series", c0 + i, sc[i])) return rc;
-        if (sc[i].ev_len + 1 > cap)
+        if (s.sc[i].ev_len + 1 > cap)
             return fail(FC_ERR_ARG, "fc_run_frame_series: cap < events + 1 for chain " + std::to_string(c0 + i));
-        ev_len[c0 + i] = sc[i].ev_len;
-        len[i] = sc[i].ev_len + 1;
+        len[i] = s.sc[i].ev_len + 1;
     }
-    DevBuf<int32_t> d_fuv, d_tidx;
-    DevBuf<int64_t> d_len;
-    DevBuf<uint64_t> d_tog;
-    DevBuf<double> d_mid;
     int q;
     const size_t outn = (size_t)nc * cap;
-    if ((q = d_fuv.alloc((size_t)2 * std::max(n_frame, 1)))) return q;
-    if ((q = d_tidx.alloc((size_t)n))) return q;
-    if ((q = d_tog.alloc(std::max<size_t>(tog.size(), 4)))) return q;
-    if ((q = d_mid.alloc((size_t)2 * std::max(n_frame, 1)))) return q;
-    if ((q = d_len.alloc((size_t)r->n_chains))) return q;
     // the large outputs are kept by the run (chunked callers ask for similar sizes)
     if ((q = r->d_fs_out.grow(2 * outn))) return q;
     if ((q = r->d_fs_cnt.grow(outn))) return q;
     double *const d_out = r->d_fs_out;
     int32_t *const d_cnt = r->d_fs_cnt;
-    if (n_frame) {
-        HIP_TRY(hipMemcpy(d_fuv, frame_u, (size_t)n_frame * 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_fuv + n_frame, frame_v, (size_t)n_frame * 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_mid, mid_xy, (size_t)n_frame * 16, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_tog, tog.data(), tog.size() * 8, hipMemcpyHostToDevice));
-    }
-    HIP_TRY(hipMemcpy(d_tidx, tog_idx.data(), (size_t)n * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_len, ev_len.data(), ev_len.size() * 8, hipMemcpyHostToDevice));
-    int e = fc::launch_frame_series(r->d_ser_a0, r->npad, r->d_events, r->ev_cap, d_len, c0, nc, n_frame, d_fuv,
-                                    d_fuv + n_frame, d_mid, cx, cy, d_tidx, d_tog, (int32_t)(tog.size() / 4), n,
-                                    cap, d_out, d_out + outn,
-                                    d_cnt, r->stream);
+    fc::FrameParams fp;
+    if ((q = frame_inputs(r, s.log, n_frame, frame_u, frame_v, mid_xy, cx, cy, fp))) return q;
+    fp.cap = cap;
+    fp.slope = d_out;
+    fp.angle = d_out + outn;
+    fp.n_cut = d_cnt;
+    const int e = fc::launch_frame(fp, fc::kFrameEvents, r->stream);
     if (e) return fail(FC_ERR_HIP, std::string("frame series: ") + hipGetErrorString((hipError_t)e));
     HIP_TRY(hipStreamSynchronize(r->stream));
     HIP_TRY(hipMemcpy(slope, d_out, outn * 8, hipMemcpyDeviceToHost));
@@ -324,59 +438,28 @@ int fc_run_frame_series_changes(fc_run *r, int32_t c0, int32_t nc, int32_t n_fra
         return fail(FC_ERR_ARG, "fc_run_frame_series_changes: null argument");
     const bool query = !t && !slope && !angle;
     if (!query && (!t || !slope || !angle)) return fail(FC_ERR_ARG, "fc_run_frame_series_changes: null output");
-    if (!r->d_events) return fail(FC_ERR_ARG, "fc_run_frame_series_changes: FC_DIAG_SERIES not enabled");
-    if (r->p.k != 2) return fail(FC_ERR_UNSUPPORTED, "fc_run_frame_series_changes: k = 2 runs only");
-    if (c0 < 0 || nc < 0 || c0 + nc > r->n_chains) return fail(FC_ERR_ARG, "fc_run_frame_series_changes: chain range");
+    CallRules rules;
+    rules.k2_only = "k = 2 runs only";
+    if (int rc = check_series_call(r, "fc_run_frame_series_changes", c0, nc, rules)) return rc;
     if (n_frame < 0 || n_frame > 256)
         return fail(FC_ERR_UNSUPPORTED, "fc_run_frame_series_changes: at most 256 frame edges");
     const int32_t n = r->g.n;
     if (int rc = check_frame_edges("fc_run_frame_series_changes", n, n_frame, frame_u, frame_v)) return rc;
     offsets[0] = 0;
     if (nc == 0) return FC_OK;
-    std::vector<fc::ChainScalars> sc;
-    if (int rc = download_scalars(r, c0, nc, sc)) return rc;
-    std::vector<int64_t> ev_len(nc), t0(nc);
-    for (int32_t i = 0; i < nc; ++i) {
-        if (int rc = check_event_overflow(r, "fc_run_frame_series_changes", c0 + i, sc[i])) return rc;
-        ev_len[i] = sc[i].ev_len;
-        t0[i] = sc[i].ser_t0;
-    }
+    SeriesCall s;
+    if (int rc = open_window(r, "fc_run_frame_series_changes", c0, nc, false, s)) return rc;
     int q;
-    // the frame tables: uploaded when the frame differs from the last call's
-    uint64_t h = fnv1a(fc::kFnvBasis, &n_frame, sizeof n_frame);
-    h = fnv1a(h, frame_u, (size_t)n_frame * 4);
-    h = fnv1a(h, frame_v, (size_t)n_frame * 4);
-    h = fnv1a(h, mid_xy, (size_t)n_frame * 16);
-    if (!r->d_fc_fuv || h != r->fc_frame_hash) {
-        std::vector<int32_t> tog_idx;
-        std::vector<uint64_t> tog;
-        build_toggles(n, n_frame, frame_u, frame_v, tog_idx, tog);
-        if ((q = r->d_fc_fuv.alloc((size_t)2 * 256))) return q;
-        if ((q = r->d_fc_tidx.alloc((size_t)n))) return q;
-        if ((q = r->d_fc_tog.alloc((size_t)4 * 512))) return q;
-        if ((q = r->d_fc_mid.alloc((size_t)2 * 256))) return q;
-        if (n_frame) {
-            HIP_TRY(hipMemcpy(r->d_fc_fuv, frame_u, (size_t)n_frame * 4, hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(r->d_fc_fuv + n_frame, frame_v, (size_t)n_frame * 4, hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(r->d_fc_mid, mid_xy, (size_t)n_frame * 16, hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(r->d_fc_tog, tog.data(), tog.size() * 8, hipMemcpyHostToDevice));
-        }
-        HIP_TRY(hipMemcpy(r->d_fc_tidx, tog_idx.data(), (size_t)n * 4, hipMemcpyHostToDevice));
-        r->fc_frame_hash = h;
-        r->fc_rows = (int32_t)(tog.size() / 4);
-    }
-    if (!r->d_fc_len) {
+    if (!r->d_fc_cnt) {
         const size_t C = (size_t)r->n_chains;
-        if ((q = r->d_fc_len.alloc(C))) return q;
-        if ((q = r->d_fc_t0.alloc(C))) return q;
         if ((q = r->d_fc_cnt.alloc(C))) return q;
         if ((q = r->d_fc_off.alloc(C))) return q;
         if ((q = r->d_fc_wcnt.alloc(C * fc::kFrameWaves))) return q;
     }
-    // the kernels index the per-chain arrays by global chain id
-    HIP_TRY(hipMemcpyAsync(r->d_fc_len + c0, ev_len.data(), (size_t)nc * 8, hipMemcpyHostToDevice, r->stream));
-    HIP_TRY(hipMemcpyAsync(r->d_fc_t0 + c0, t0.data(), (size_t)nc * 8, hipMemcpyHostToDevice, r->stream));
-    int32_t *const d_fuv = r->d_fc_fuv;
+    fc::FrameParams fp;
+    if ((q = frame_inputs(r, s.log, n_frame, frame_u, frame_v, mid_xy, cx, cy, fp))) return q;
+    fp.cp_cnt = r->d_fc_cnt;
+    fp.wcnt = r->d_fc_wcnt;
     // one pass (count and write together) into per-wave staging ranges when they fit a tenth of
     // the free device memory: sized by event_cap, kept by the run
     const int64_t nk = (r->ev_cap + 63) / 64;
@@ -399,16 +482,14 @@ int fc_run_frame_series_changes(fc_run *r, int32_t c0, int32_t nc, int32_t n_fra
     }
     if (!query) r->series_staged = staged ? 1 : 0;
     const size_t stn = r->d_st_sa.capacity() / 2;  // staging: slope at d_st_sa, angle at d_st_sa + stn
-    int e;
-    if (staged)
-        e = fc::launch_frame_stage(r->d_ser_a0, r->npad, r->d_events, r->ev_cap, r->d_fc_len, c0, nc, n_frame, d_fuv,
-                                   d_fuv + n_frame, r->d_fc_mid, cx, cy, r->d_fc_tidx, r->d_fc_tog, r->fc_rows, n,
-                                   r->d_fc_t0, r->d_fc_cnt, stage_cap, r->d_st_t, r->d_st_sa, r->d_st_sa + stn,
-                                   r->d_fc_wcnt, r->stream);
-    else  // pass 1: change points per chain -> offsets
-        e = fc::launch_frame_changes(r->d_ser_a0, r->npad, r->d_events, r->ev_cap, r->d_fc_len, c0, nc, n_frame, d_fuv,
-                                     d_fuv + n_frame, r->d_fc_mid, cx, cy, r->d_fc_tidx, r->d_fc_tog, r->fc_rows, n,
-                                     r->d_fc_t0, r->d_fc_cnt, nullptr, nullptr, nullptr, nullptr, r->d_fc_wcnt, r->stream);
+    if (staged) {
+        fp.cap = stage_cap;
+        fp.t_out = r->d_st_t;
+        fp.slope = r->d_st_sa;
+        fp.angle = r->d_st_sa + stn;
+    }
+    // (two passes: the first counts the change points per chain -> offsets)
+    int e = fc::launch_frame(fp, staged ? fc::kFrameStage : fc::kFrameCount, r->stream);
     if (e) return fail(FC_ERR_HIP, std::string(staged ? "frame changes (stage): " : "frame changes (count): ") +
                                        hipGetErrorString((hipError_t)e));
     std::vector<int64_t> cnt(nc);
@@ -430,13 +511,16 @@ int fc_run_frame_series_changes(fc_run *r, int32_t c0, int32_t nc, int32_t n_fra
     // pass 2: (t, slope, angle) at the offsets, then one copy per array
     HIP_TRY(hipMemcpyAsync(r->d_fc_off, offsets, (size_t)nc * 8, hipMemcpyHostToDevice, r->stream));
     double *const d_sl = r->d_fc_sa, *const d_an = r->d_fc_sa + r->d_fc_sa.capacity() / 2;
-    if (staged)  // the staged ranges packed at the offsets
+    if (staged) {  // the staged ranges packed at the offsets
         e = fc::launch_frame_compact(nc, stage_cap, r->d_st_t, r->d_st_sa, r->d_st_sa + stn, r->d_fc_wcnt, r->d_fc_off,
                                      r->d_fc_t, d_sl, d_an, r->stream);
-    else
-        e = fc::launch_frame_changes(r->d_ser_a0, r->npad, r->d_events, r->ev_cap, r->d_fc_len, c0, nc, n_frame, d_fuv,
-                                     d_fuv + n_frame, r->d_fc_mid, cx, cy, r->d_fc_tidx, r->d_fc_tog, r->fc_rows, n,
-                                     r->d_fc_t0, r->d_fc_cnt, r->d_fc_off, r->d_fc_t, d_sl, d_an, r->d_fc_wcnt, r->stream);
+    } else {
+        fp.cp_off = r->d_fc_off;
+        fp.t_out = r->d_fc_t;
+        fp.slope = d_sl;
+        fp.angle = d_an;
+        e = fc::launch_frame(fp, fc::kFrameWrite, r->stream);
+    }
     if (e) return fail(FC_ERR_HIP, std::string("frame changes (write): ") + hipGetErrorString((hipError_t)e));
     HIP_TRY(hipMemcpyAsync(t, r->d_fc_t, (size_t)total * 8, hipMemcpyDeviceToHost, r->stream));
     HIP_TRY(hipMemcpyAsync(slope, d_sl, (size_t)total * 8, hipMemcpyDeviceToHost, r->stream));
@@ -476,9 +560,8 @@ int fc_run_set_elections(fc_run *r, int32_t n_cols, const int32_t *node_cols, in
     if (n_elections < 0 || n_elections > fc::kVoteMaxElections)
         return fail(FC_ERR_ARG, "fc_run_set_elections: n_elections must be 0..4");
     if (n_elections > 0 && (!col_a || !col_b)) return fail(FC_ERR_ARG, "fc_run_set_elections: null election columns");
-    if (n_gap_edges < 0 || n_gap_edges > fc::kVoteMaxEdges)
-        return fail(FC_ERR_ARG, "fc_run_set_elections: n_gap_edges must be 0..256");
-    if (n_gap_edges > 0 && !gap_edges) return fail(FC_ERR_ARG, "fc_run_set_elections: null gap_edges");
+    if (int rc = check_hist_edges("fc_run_set_elections", "gap_edges", n_gap_edges, fc::kVoteMaxEdges, gap_edges))
+        return rc;
     const int32_t n = r->g.n;
     for (int32_t j = 0; j < n_cols; ++j) {
         int64_t tot = 0;
@@ -495,9 +578,6 @@ int fc_run_set_elections(fc_run *r, int32_t n_cols, const int32_t *node_cols, in
         if (col_a[e] < 0 || col_a[e] >= n_cols || col_b[e] < 0 || col_b[e] >= n_cols || col_a[e] == col_b[e])
             return fail(FC_ERR_ARG, "fc_run_set_elections: election " + std::to_string(e) +
                                         " needs two different columns below n_cols");
-    for (int32_t i = 1; i < n_gap_edges; ++i)
-        if (gap_edges[i] <= gap_edges[i - 1])
-            return fail(FC_ERR_ARG, "fc_run_set_elections: gap_edges must be strictly ascending");
     // rows padded to the kernel instance's column count
     const int32_t ncp = fc::votes_padded_cols(n_cols);
     std::vector<int32_t> cols((size_t)n * ncp, 0);
@@ -520,50 +600,24 @@ int fc_run_set_elections(fc_run *r, int32_t n_cols, const int32_t *node_cols, in
 int fc_run_election_series(fc_run *r, int32_t c0, int32_t nc, int64_t *tally_now, int64_t *tally_sum,
                            int64_t *seats_hist, int64_t *wins_sum, int64_t *gap_sum, int64_t *gap_hist) {
     if (!r) return fail(FC_ERR_ARG, "fc_run_election_series: null run");
-    if (r->p.proposal == FC_PROPOSE_RECOM)
-        return fail(FC_ERR_UNSUPPORTED, "fc_run_election_series: the election series replays the flip log (not ReCom)");
-    if (!r->d_events) return fail(FC_ERR_ARG, "fc_run_election_series: FC_DIAG_SERIES not enabled");
-    if (r->el_n_cols == 0) return fail(FC_ERR_ARG, "fc_run_election_series: call fc_run_set_elections first");
-    if (c0 < 0 || nc < 0 || c0 + nc > r->n_chains) return fail(FC_ERR_ARG, "fc_run_election_series: chain range");
+    if (int rc = check_series_call(r, "fc_run_election_series", c0, nc,
+                                   {"the election series", r->el_n_cols ? nullptr : "fc_run_set_elections"}))
+        return rc;
     if (gap_hist && r->el_n_edges == 0)
         return fail(FC_ERR_ARG, "fc_run_election_series: gap_hist needs gap_edges (fc_run_set_elections)");
     if (nc == 0) return FC_OK;
-    std::vector<fc::ChainScalars> sc;
-    if (int rc = download_scalars(r, c0, nc, sc)) return rc;
-    std::vector<int64_t> meta((size_t)3 * nc);
-    for (int32_t i = 0; i < nc; ++i) {
-        if (int rc = check_event_overflow(r, "fc_run_election_series", c0 + i, sc[i])) return rc;
-        if (sc[i].steps - sc[i].ser_t0 + 1 >= (int64_t(1) << 30))
-            return fail(FC_ERR_ARG, "fc_run_election_series: chain " + std::to_string(c0 + i) +
-                                        "'s window has 2^30 yields or more; reset the series window more often");
-        meta[i] = sc[i].ev_len;
-        meta[(size_t)nc + i] = sc[i].ser_t0;
-        meta[(size_t)2 * nc + i] = sc[i].steps + 1;
-    }
+    SeriesCall s;
+    if (int rc = open_window(r, "fc_run_election_series", c0, nc, true, s)) return rc;
     const int32_t k = r->p.k, n_cols = r->el_n_cols, n_el = r->el_n_el, n_edges = r->el_n_edges;
-    // the outputs, one after the other in one device buffer
-    const size_t sz[6] = {(size_t)nc * k * n_cols, (size_t)nc * k * n_cols, (size_t)nc * n_el * (k + 1),
-                          (size_t)nc * n_el * k,   (size_t)nc * n_el,       (size_t)nc * n_el * (n_edges + 1)};
-    size_t off[7] = {0};
-    for (int i = 0; i < 6; ++i) off[i + 1] = off[i] + sz[i];
+    OutPack out;
     int q;
-    if ((q = r->d_el_meta.grow(meta.size()))) return q;
-    if ((q = r->d_el_out.grow(off[6]))) return q;
+    if ((q = out.reserve(r, {(size_t)nc * k * n_cols, (size_t)nc * k * n_cols, (size_t)nc * n_el * (k + 1),
+                             (size_t)nc * n_el * k, (size_t)nc * n_el, (size_t)nc * n_el * (n_edges + 1)})))
+        return q;
     const bool global_cur = (r->p.flags & FC_FLAG_VOTES_GLOBAL_CUR) || !fc::votes_cur_in_lds(r->npad, k, n_edges);
     if (global_cur && (q = r->d_el_cur.grow((size_t)nc * r->npad))) return q;
-    HIP_TRY(hipMemcpyAsync(r->d_el_meta, meta.data(), meta.size() * 8, hipMemcpyHostToDevice, r->stream));
     fc::VotesParams vp{};
-    vp.a0 = r->d_ser_a0;
-    vp.npad = r->npad;
-    vp.n = r->g.n;
-    vp.k = k;
-    vp.events = r->d_events;
-    vp.ev_cap = r->ev_cap;
-    vp.ev_len = r->d_el_meta;
-    vp.t0 = r->d_el_meta + nc;
-    vp.t_end = r->d_el_meta + 2 * (size_t)nc;
-    vp.c0 = c0;
-    vp.nc = nc;
+    vp.log = s.log;
     vp.cols = r->d_el_cols;
     vp.n_cols = n_cols;
     vp.n_el = n_el;
@@ -574,21 +628,15 @@ int fc_run_election_series(fc_run *r, int32_t c0, int32_t nc, int64_t *tally_now
     vp.n_edges = n_edges;
     vp.edges = r->d_el_edges;
     vp.cur = global_cur ? r->d_el_cur.get() : nullptr;
-    int64_t *const d_out = r->d_el_out;
-    vp.tally_now = d_out + off[0];
-    vp.tally_sum = d_out + off[1];
-    vp.seats_hist = d_out + off[2];
-    vp.wins_sum = d_out + off[3];
-    vp.gap_sum = d_out + off[4];
-    vp.gap_hist = d_out + off[5];
+    vp.tally_now = out.at(0);
+    vp.tally_sum = out.at(1);
+    vp.seats_hist = out.at(2);
+    vp.wins_sum = out.at(3);
+    vp.gap_sum = out.at(4);
+    vp.gap_hist = out.at(5);
     const int e = fc::launch_votes(vp, global_cur, r->stream);
     if (e) return fail(FC_ERR_HIP, std::string("election series: ") + hipGetErrorString((hipError_t)e));
-    int64_t *const host[6] = {tally_now, tally_sum, seats_hist, wins_sum, gap_sum, gap_hist};
-    for (int i = 0; i < 6; ++i)
-        if (host[i] && sz[i])
-            HIP_TRY(hipMemcpyAsync(host[i], d_out + off[i], sz[i] * 8, hipMemcpyDeviceToHost, r->stream));
-    HIP_TRY(hipStreamSynchronize(r->stream));
-    return FC_OK;
+    return out.fetch(r, {tally_now, tally_sum, seats_hist, wins_sum, gap_sum, gap_hist});
 }
 
 // ---- compactness series (fc_shapes.h, fc_shapes.hip) ---------------------------
@@ -609,9 +657,7 @@ int fc_run_set_shapes(fc_run *r, const int32_t *node_area, const int32_t *node_e
     if (!r->d_events) return fail(FC_ERR_ARG, "fc_run_set_shapes: FC_DIAG_SERIES not enabled");
     const int32_t n = r->g.n, E = r->g.n_edges;
     if (E > 0 && !edge_len) return fail(FC_ERR_ARG, "fc_run_set_shapes: null edge_len");
-    if (n_pp_edges < 0 || n_pp_edges > fc::kShapeMaxEdges)
-        return fail(FC_ERR_ARG, "fc_run_set_shapes: n_pp_edges must be 0..64");
-    if (n_pp_edges > 0 && !pp_edges) return fail(FC_ERR_ARG, "fc_run_set_shapes: null pp_edges");
+    if (int rc = check_hist_edges("fc_run_set_shapes", "pp_edges", n_pp_edges, fc::kShapeMaxEdges, pp_edges)) return rc;
     int64_t area = 0, perim = 0;
     for (int32_t u = 0; u < n; ++u) {
         if (node_area[u] < 0 || (node_ext && node_ext[u] < 0))
@@ -626,9 +672,6 @@ int fc_run_set_shapes(fc_run *r, const int32_t *node_area, const int32_t *node_e
     if (area > INT32_MAX) return fail(FC_ERR_ARG, "fc_run_set_shapes: node_area totals over 2^31 - 1");
     if (perim > INT32_MAX)
         return fail(FC_ERR_ARG, "fc_run_set_shapes: node_ext and edge_len together total over 2^31 - 1");
-    for (int32_t i = 1; i < n_pp_edges; ++i)
-        if (pp_edges[i] <= pp_edges[i - 1])
-            return fail(FC_ERR_ARG, "fc_run_set_shapes: pp_edges must be strictly ascending");
     const int32_t W = fc::shapes_row_width(r->g.max_degree);
     if (W == 0) return fail(FC_ERR_UNSUPPORTED, "fc_run_set_shapes: node degree above 16");
     if (!fc::shapes_fit_lds(r->npad, r->p.k, n_pp_edges, W))
@@ -660,70 +703,37 @@ int fc_run_shape_series(fc_run *r, int32_t c0, int32_t nc, int64_t *area_now, in
                         int64_t *pp_now, int64_t *pp_sum, int64_t *pp_min_sum, int64_t *pp_hist,
                         int64_t *pp_min_hist) {
     if (!r) return fail(FC_ERR_ARG, "fc_run_shape_series: null run");
-    if (r->p.proposal == FC_PROPOSE_RECOM)
-        return fail(FC_ERR_UNSUPPORTED, "fc_run_shape_series: the compactness series replays the flip log (not ReCom)");
-    if (!r->d_events) return fail(FC_ERR_ARG, "fc_run_shape_series: FC_DIAG_SERIES not enabled");
-    if (r->sh_width == 0) return fail(FC_ERR_ARG, "fc_run_shape_series: call fc_run_set_shapes first");
-    if (c0 < 0 || nc < 0 || c0 + nc > r->n_chains) return fail(FC_ERR_ARG, "fc_run_shape_series: chain range");
+    if (int rc = check_series_call(r, "fc_run_shape_series", c0, nc,
+                                   {"the compactness series", r->sh_width ? nullptr : "fc_run_set_shapes"}))
+        return rc;
     if ((pp_hist || pp_min_hist) && r->sh_n_edges == 0)
         return fail(FC_ERR_ARG, "fc_run_shape_series: the histograms need pp_edges (fc_run_set_shapes)");
     if (nc == 0) return FC_OK;
-    std::vector<fc::ChainScalars> sc;
-    if (int rc = download_scalars(r, c0, nc, sc)) return rc;
-    std::vector<int64_t> meta((size_t)3 * nc);
-    for (int32_t i = 0; i < nc; ++i) {
-        if (int rc = check_event_overflow(r, "fc_run_shape_series", c0 + i, sc[i])) return rc;
-        if (sc[i].steps - sc[i].ser_t0 + 1 >= (int64_t(1) << 30))
-            return fail(FC_ERR_ARG, "fc_run_shape_series: chain " + std::to_string(c0 + i) +
-                                        "'s window has 2^30 yields or more; reset the series window more often");
-        meta[i] = sc[i].ev_len;
-        meta[(size_t)nc + i] = sc[i].ser_t0;
-        meta[(size_t)2 * nc + i] = sc[i].steps + 1;
-    }
+    SeriesCall s;
+    if (int rc = open_window(r, "fc_run_shape_series", c0, nc, true, s)) return rc;
     const int32_t k = r->p.k, n_edges = r->sh_n_edges;
-    // the outputs, one after the other in one device buffer
     const size_t ck = (size_t)nc * k, nbins = (size_t)n_edges + 1;
-    const size_t sz[8] = {ck, ck, ck, ck, ck, (size_t)nc, ck * nbins, (size_t)nc * nbins};
-    size_t off[9] = {0};
-    for (int i = 0; i < 8; ++i) off[i + 1] = off[i] + sz[i];
-    int q;
-    if ((q = r->d_sh_meta.grow(meta.size()))) return q;
-    if ((q = r->d_sh_out.grow(off[8]))) return q;
-    HIP_TRY(hipMemcpyAsync(r->d_sh_meta, meta.data(), meta.size() * 8, hipMemcpyHostToDevice, r->stream));
+    OutPack out;
+    if (int rc = out.reserve(r, {ck, ck, ck, ck, ck, (size_t)nc, ck * nbins, (size_t)nc * nbins})) return rc;
     fc::ShapesParams sp{};
-    sp.a0 = r->d_ser_a0;
-    sp.npad = r->npad;
-    sp.n = r->g.n;
-    sp.k = k;
-    sp.events = r->d_events;
-    sp.ev_cap = r->ev_cap;
-    sp.ev_len = r->d_sh_meta;
-    sp.t0 = r->d_sh_meta + nc;
-    sp.t_end = r->d_sh_meta + 2 * (size_t)nc;
-    sp.c0 = c0;
-    sp.nc = nc;
+    sp.log = s.log;
     sp.rows = r->d_sh_rows;
     sp.nodes = r->d_sh_nodes;
     sp.width = r->sh_width;
     sp.n_edges = n_edges;
     sp.edges = r->d_sh_edges;
-    int64_t *const d_out = r->d_sh_out;
-    sp.area_now = d_out + off[0];
-    sp.perim_now = d_out + off[1];
-    sp.perim_sum = d_out + off[2];
-    sp.pp_now = d_out + off[3];
-    sp.pp_sum = d_out + off[4];
-    sp.pp_min_sum = d_out + off[5];
-    sp.pp_hist = d_out + off[6];
-    sp.pp_min_hist = d_out + off[7];
+    sp.area_now = out.at(0);
+    sp.perim_now = out.at(1);
+    sp.perim_sum = out.at(2);
+    sp.pp_now = out.at(3);
+    sp.pp_sum = out.at(4);
+    sp.pp_min_sum = out.at(5);
+    sp.pp_hist = out.at(6);
+    sp.pp_min_hist = out.at(7);
     const int e = fc::launch_shapes(sp, r->stream);
     if (e) return fail(FC_ERR_HIP, std::string("compactness series: ") + hipGetErrorString((hipError_t)e));
-    int64_t *const host[8] = {area_now, perim_now, perim_sum, pp_now, pp_sum, pp_min_sum, pp_hist, pp_min_hist};
-    for (int i = 0; i < 8; ++i)
-        if (host[i] && sz[i] && (i < 6 || n_edges > 0))
-            HIP_TRY(hipMemcpyAsync(host[i], d_out + off[i], sz[i] * 8, hipMemcpyDeviceToHost, r->stream));
-    HIP_TRY(hipStreamSynchronize(r->stream));
-    return FC_OK;
+    // (without pp_edges the kernel writes no histogram, and the check above has left no pointer to one)
+    return out.fetch(r, {area_now, perim_now, perim_sum, pp_now, pp_sum, pp_min_sum, pp_hist, pp_min_hist});
 }
 
 int fc_run_read_hist(fc_run *r, int64_t *cut_hist, int64_t *nb_hist) {

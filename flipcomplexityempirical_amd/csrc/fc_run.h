@@ -137,11 +137,17 @@ struct fc_run : fc::RunShape {
     DevBuf<uint32_t> d_nbe, d_eslot;  // recom: neighbour rows, edge ends' row indices
     DevBuf<uint64_t> d_recom_thresh;  // recom: [2E+1] acceptance thresholds
     DevBuf<int8_t> d_ser_a0;   // FC_DIAG_SERIES: assignment at the series window start
+    // The series calls (fc_readout.cpp open_window / OutPack) share two buffers, grown on demand.
+    // Every call fills what it reads of them and synchronises before it returns, so nothing is
+    // carried from one call to the next
+    DevBuf<int64_t> d_ser_meta;  // per call: ev_len, t0, t_end of the chains read, [nc] each (LogWindow)
+    DevBuf<int64_t> d_ser_out;   // per call: the int64 outputs of the election / compactness series,
+                                 // one after the other
     DevBuf<double> d_fs_out;   // fc_run_frame_series output (slope, angle), grown on demand
     DevBuf<int32_t> d_fs_cnt;  // ... frame-cut counts
     // fc_run_frame_series_changes, kept across calls (one call per launch in the driver loop):
-    // the frame tables (re-uploaded only when the frame changes), per-chain lengths / window
-    // starts / counts / offsets, and the (t, slope, angle) outputs, grown on demand
+    // the frame tables (fc_run_frame_series' too; re-uploaded only when the frame changes), per-chain counts / offsets
+    // (sized for every chain of the run), and the (t, slope, angle) outputs, grown on demand
     uint64_t fc_frame_hash = 0;
     int32_t fc_rows = 0;  // rows of d_fc_tog
     DevBuf<int64_t> d_fc_wcnt;  // change points per chain and frame-series wave
@@ -150,7 +156,7 @@ struct fc_run : fc::RunShape {
     DevBuf<int32_t> d_fc_fuv, d_fc_tidx;
     DevBuf<uint64_t> d_fc_tog;
     DevBuf<double> d_fc_mid;
-    DevBuf<int64_t> d_fc_len, d_fc_t0, d_fc_cnt, d_fc_off;
+    DevBuf<int64_t> d_fc_cnt, d_fc_off;
     DevBuf<int64_t> d_fc_t;
     DevBuf<double> d_fc_sa;     // [2 * change points the outputs hold]
     // election series (fc_run_set_elections; fc_votes.h, fc_votes.hip).  el_n_cols 0: not set
@@ -158,16 +164,12 @@ struct fc_run : fc::RunShape {
     int32_t el_col_a[fc::kVoteMaxElections] = {0}, el_col_b[fc::kVoteMaxElections] = {0};
     DevBuf<int32_t> d_el_cols;    // [n * votes_padded_cols(el_n_cols)]
     DevBuf<int64_t> d_el_edges;   // [el_n_edges]
-    DevBuf<int64_t> d_el_meta;    // per call: ev_len, t0, t_end of the chains read, [nc] each
-    DevBuf<int64_t> d_el_out;     // per call: the six outputs, one after the other
     DevBuf<int8_t> d_el_cur;      // per call: current-assignment rows when they are not kept in LDS
     // compactness series (fc_run_set_shapes; fc_shapes.h, fc_shapes.hip).  sh_width 0: not set
     int32_t sh_width = 0, sh_n_edges = 0;
     DevBuf<fc::ShapeSlot> d_sh_rows;   // [n * sh_width] neighbour rows
     DevBuf<fc::ShapeNode> d_sh_nodes;  // [n]
     DevBuf<int64_t> d_sh_edges;   // [sh_n_edges]
-    DevBuf<int64_t> d_sh_meta;    // per call: ev_len, t0, t_end of the chains read, [nc] each
-    DevBuf<int64_t> d_sh_out;     // per call: the eight outputs, one after the other
     char kname[96] = {0};       // last launched flip-kernel instance
     // replica exchange (fc_run_set_ladders; fc_ladder.h, fc_exchange.hip).  Slots are flat: ladder
     // l's rung r is slot lad_off[l] + r

@@ -21,15 +21,16 @@ __global__ __launch_bounds__(kThreads) void series_expand_kernel(const fc_event 
                                                                  const int32_t *__restrict__ cut0,
                                                                  const int64_t *__restrict__ len, int32_t c0,
                                                                  int64_t stride, uint16_t *__restrict__ x) {
+    // the per-chain arrays are the call's (fc_replay.h): [nc], indexed by cl
     const int32_t cl = (int32_t)blockIdx.y;
     const int32_t c = c0 + cl;
-    const int64_t L = len[c];
+    const int64_t L = len[cl];
     const int64_t base_t = (int64_t)blockIdx.x * kTile;
     if (base_t >= L) return;
     const fc_event *ev = events + (size_t)c * ev_cap;
-    const int64_t ne = ev_len[c] < ev_cap ? ev_len[c] : ev_cap;
-    const int64_t tw = t0[c];
-    const int32_t x0 = cut0[c];
+    const int64_t ne = ev_len[cl] < ev_cap ? ev_len[cl] : ev_cap;
+    const int64_t tw = t0[cl];
+    const int32_t x0 = cut0[cl];
     // events are sorted by t: the value at yield tw + t is the cut of the last event with
     // ev.t <= tw + t (the window's initial |cut| before the first one)
     for (int i = threadIdx.x; i < kTile; i += kThreads) {
@@ -65,8 +66,8 @@ __global__ __launch_bounds__(kThreads) void series_lagsum_kernel(const uint16_t 
     __shared__ uint16_t tile[kTile];
     __shared__ int64_t red[kThreads / 64];
     const int32_t cl = (int32_t)blockIdx.y;
-    const int32_t c = c0 + cl;
-    const int64_t L = len[c];
+    const int32_t c = c0 + cl;  // (sums holds every chain of the run)
+    const int64_t L = len[cl];
     const int64_t base_t = (int64_t)blockIdx.x * kTile;
     if (base_t >= L) return;
     const uint16_t *xc = x + (size_t)cl * stride;
@@ -225,7 +226,7 @@ __global__ __launch_bounds__(64 * kFsWaves) void frame_series_kernel(
     const int32_t c = c0 + cl;
     const int8_t *a = a0 + (size_t)c * npad;
     const fc_event *ev = events + (size_t)c * ev_cap;
-    const int64_t ne = ev_len[c];
+    const int64_t ne = ev_len[cl] < ev_cap ? ev_len[cl] : ev_cap;  // (ev_len, t0: [nc], indexed by cl)
     auto row_of = [&](int v) -> int32_t { return LT ? (int32_t)ti16[v] : tog_idx[v]; };
     // this wave's chunk range [k0, k1)
     const int64_t nk = (ne + 63) >> 6;
@@ -302,7 +303,7 @@ __global__ __launch_bounds__(64 * kFsWaves) void frame_series_kernel(
                 } else if constexpr (MODE >= 2) {
                     so[0] = sl;
                     ao[0] = an;
-                    to[0] = t0[c];
+                    to[0] = t0[cl];
                 }
             }
         }
@@ -480,79 +481,39 @@ int launch_series_lagsums(const uint16_t *x, const int64_t *len, int32_t c0, int
     return (int)hipGetLastError();
 }
 
-}  // namespace fc
+namespace {
 
-namespace fc {
-
-int launch_frame_series(const int8_t *a0, int32_t npad, const fc_event *events, int64_t ev_cap,
-                        const int64_t *ev_len, int32_t c0, int32_t nc, int32_t n_frame, const int32_t *fu,
-                        const int32_t *fv, const double *mid, double cx, double cy, const int32_t *tog_idx,
-                        const uint64_t *tog_mask, int32_t n_rows, int32_t n_nodes, int64_t cap, double *slope,
-                        double *angle, int32_t *cnt, void *stream) {
-    if (nc <= 0) return (int)hipSuccess;
-    if (n_frame > 64 * kFrameWords) return (int)hipErrorInvalidValue;
-    const dim3 grid((unsigned)nc), block(64 * kFsWaves);
-    const size_t lds = frame_lds_bytes(n_frame, n_rows, n_nodes);
-#define FC_FS_ARGS a0, npad, events, ev_cap, ev_len, c0, nc, n_frame, fu, fv, mid, cx, cy, tog_idx, tog_mask, n_rows, n_nodes
-    if (lds)
-        hipLaunchKernelGGL((frame_series_kernel<0, true>), grid, block, lds, (hipStream_t)stream, FC_FS_ARGS,
-                           cap, slope, angle, cnt, (const int64_t *)nullptr, (int64_t *)nullptr,
-                           (const int64_t *)nullptr, (int64_t *)nullptr, (int64_t *)nullptr);
-    else
-        hipLaunchKernelGGL((frame_series_kernel<0, false>), grid, block, 0, (hipStream_t)stream, FC_FS_ARGS,
-                           cap, slope, angle, cnt, (const int64_t *)nullptr, (int64_t *)nullptr,
-                           (const int64_t *)nullptr, (int64_t *)nullptr, (int64_t *)nullptr);
-    return (int)hipGetLastError();
+// the one place that spells the kernel's positional arguments
+template <int MODE, bool LT>
+void launch_frame_as(const FrameParams &p, size_t lds, hipStream_t stream) {
+    const LogWindow &w = p.log;
+    hipLaunchKernelGGL((frame_series_kernel<MODE, LT>), dim3((unsigned)w.nc), dim3(64 * kFsWaves), lds, stream, w.a0,
+                       w.npad, w.events, w.ev_cap, w.ev_len, w.c0, w.nc, p.n_frame, p.fu, p.fv, p.mid, p.cx, p.cy,
+                       p.tog_idx, p.tog_mask, p.n_rows, w.n, p.cap, p.slope, p.angle, p.n_cut, w.t0, p.cp_cnt, p.cp_off,
+                       p.t_out, p.wcnt);
 }
 
-int launch_frame_changes(const int8_t *a0, int32_t npad, const fc_event *events, int64_t ev_cap,
-                         const int64_t *ev_len, int32_t c0, int32_t nc, int32_t n_frame, const int32_t *fu,
-                         const int32_t *fv, const double *mid, double cx, double cy, const int32_t *tog_idx,
-                         const uint64_t *tog_mask, int32_t n_rows, int32_t n_nodes, const int64_t *t0,
-                         int64_t *cp_cnt, const int64_t *cp_off, int64_t *t_out, double *slope, double *angle,
-                         int64_t *wcnt, void *stream) {
-    if (nc <= 0) return (int)hipSuccess;
-    if (n_frame > 64 * kFrameWords) return (int)hipErrorInvalidValue;
-    const dim3 grid((unsigned)nc), block(64 * kFsWaves);
-    const size_t lds = frame_lds_bytes(n_frame, n_rows, n_nodes);
-    if (!cp_off) {
-        if (lds)
-            hipLaunchKernelGGL((frame_series_kernel<1, true>), grid, block, lds, (hipStream_t)stream, FC_FS_ARGS,
-                               (int64_t)0, (double *)nullptr, (double *)nullptr, (int32_t *)nullptr, t0, cp_cnt, cp_off,
-                               t_out, wcnt);
-        else
-            hipLaunchKernelGGL((frame_series_kernel<1, false>), grid, block, 0, (hipStream_t)stream, FC_FS_ARGS,
-                               (int64_t)0, (double *)nullptr, (double *)nullptr, (int32_t *)nullptr, t0, cp_cnt, cp_off,
-                               t_out, wcnt);
-    } else {
-        if (lds)
-            hipLaunchKernelGGL((frame_series_kernel<2, true>), grid, block, lds, (hipStream_t)stream, FC_FS_ARGS,
-                               (int64_t)0, slope, angle, (int32_t *)nullptr, t0, cp_cnt, cp_off, t_out, wcnt);
-        else
-            hipLaunchKernelGGL((frame_series_kernel<2, false>), grid, block, 0, (hipStream_t)stream, FC_FS_ARGS,
-                               (int64_t)0, slope, angle, (int32_t *)nullptr, t0, cp_cnt, cp_off, t_out, wcnt);
+template <int MODE>
+void launch_frame_mode(const FrameParams &p, hipStream_t stream) {
+    const size_t lds = frame_lds_bytes(p.n_frame, p.n_rows, p.log.n);
+    if (lds)
+        launch_frame_as<MODE, true>(p, lds, stream);
+    else
+        launch_frame_as<MODE, false>(p, 0, stream);
+}
+
+}  // namespace
+
+int launch_frame(const FrameParams &p, int mode, void *stream) {
+    if (p.log.nc <= 0) return (int)hipSuccess;
+    if (p.n_frame > 64 * kFrameWords) return (int)hipErrorInvalidValue;
+    switch (mode) {
+    case kFrameEvents: launch_frame_mode<kFrameEvents>(p, (hipStream_t)stream); break;
+    case kFrameCount: launch_frame_mode<kFrameCount>(p, (hipStream_t)stream); break;
+    case kFrameWrite: launch_frame_mode<kFrameWrite>(p, (hipStream_t)stream); break;
+    case kFrameStage: launch_frame_mode<kFrameStage>(p, (hipStream_t)stream); break;
+    default: return (int)hipErrorInvalidValue;
     }
-    return (int)hipGetLastError();
-}
-
-int launch_frame_stage(const int8_t *a0, int32_t npad, const fc_event *events, int64_t ev_cap,
-                       const int64_t *ev_len, int32_t c0, int32_t nc, int32_t n_frame, const int32_t *fu,
-                       const int32_t *fv, const double *mid, double cx, double cy, const int32_t *tog_idx,
-                       const uint64_t *tog_mask, int32_t n_rows, int32_t n_nodes, const int64_t *t0,
-                       int64_t *cp_cnt, int64_t stage_cap, int64_t *st_t, double *st_s, double *st_a,
-                       int64_t *wcnt, void *stream) {
-    if (nc <= 0) return (int)hipSuccess;
-    if (n_frame > 64 * kFrameWords) return (int)hipErrorInvalidValue;
-    const dim3 grid((unsigned)nc), block(64 * kFsWaves);
-    const size_t lds = frame_lds_bytes(n_frame, n_rows, n_nodes);
-    if (lds)
-        hipLaunchKernelGGL((frame_series_kernel<3, true>), grid, block, lds, (hipStream_t)stream, FC_FS_ARGS,
-                           stage_cap, st_s, st_a, (int32_t *)nullptr, t0, cp_cnt, (const int64_t *)nullptr, st_t,
-                           wcnt);
-    else
-        hipLaunchKernelGGL((frame_series_kernel<3, false>), grid, block, 0, (hipStream_t)stream, FC_FS_ARGS,
-                           stage_cap, st_s, st_a, (int32_t *)nullptr, t0, cp_cnt, (const int64_t *)nullptr, st_t,
-                           wcnt);
     return (int)hipGetLastError();
 }
 
@@ -564,6 +525,5 @@ int launch_frame_compact(int32_t nc, int64_t stage_cap, const int64_t *st_t, con
                        st_a, stage_cap, wcnt, cp_off, t_out, slope, angle);
     return (int)hipGetLastError();
 }
-#undef FC_FS_ARGS
 
 }  // namespace fc

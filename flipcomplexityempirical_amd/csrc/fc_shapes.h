@@ -9,8 +9,8 @@
 #pragma once
 #include <stdint.h>
 
-#include "../../include/flipchain.h"
 #include "fc_philox.h"  // FC_HD
+#include "fc_replay.h"
 
 namespace fc {
 
@@ -36,14 +36,7 @@ struct alignas(8) ShapeNode {
 
 // Kernel parameters (passed by value).  Output rows are per chain of the call, [nc] rows each.
 struct ShapesParams {
-    const int8_t *a0;         // [n_chains * npad] assignment at the series window start
-    int32_t npad, n, k;
-    const fc_event *events;   // [n_chains * ev_cap]
-    int64_t ev_cap;
-    const int64_t *ev_len;    // [nc] events of chain c0 + i
-    const int64_t *t0;        // [nc] first yield of the window
-    const int64_t *t_end;     // [nc] last yield of the window + 1
-    int32_t c0, nc;
+    LogWindow log;            // the chains read and their window (fc_replay.h)
     const ShapeSlot *rows;    // [n * width] neighbour rows
     const ShapeNode *nodes;   // [n]
     int32_t width;            // slots per row: 8 or 16

@@ -19,17 +19,14 @@
 // in LDS before the next event reads it.
 #include <hip/hip_runtime.h>
 
+#include "fc_device.h"
 #include "fc_shapes.h"
 
 namespace fc {
 namespace {
 
-__device__ __forceinline__ int32_t rl32(int32_t x, int l) { return __builtin_amdgcn_readlane(x, l); }
-__device__ __forceinline__ int64_t rl64(int64_t x, int l) {
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int32_t)(uint32_t)x, l);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int32_t)(uint32_t)((uint64_t)x >> 32), l);
-    return (int64_t)(((uint64_t)hi << 32) | lo);
-}
+using dev::rl32;
+using dev::rl64;
 
 // x of the lane a DPP control pairs this one with (every lane has a partner under these controls)
 template <int CTRL>
@@ -69,8 +66,9 @@ __global__ __launch_bounds__(64) void shapes_kernel(const ShapesParams p) {
     constexpr int RV = W / 2;  // 16-byte pieces of a row
     const int lane = (int)threadIdx.x;
     const int32_t cl = (int32_t)blockIdx.x;
-    const int32_t c = p.c0 + cl;
-    const int32_t k = p.k, n = p.n, n_edges = p.n_edges;
+    const LogWindow &w = p.log;
+    const int32_t c = w.c0 + cl;
+    const int32_t k = w.k, n = w.n, n_edges = p.n_edges;
     const int32_t nb = n_edges + 1;
     int64_t *hist = (int64_t *)smem;                                   // [k + 1][nb], the last row Qmin's
     int32_t *tab = (int32_t *)(smem + shapes_hist_bytes(k, n_edges));  // [2][32] initial areas, perimeters
@@ -80,7 +78,7 @@ __global__ __launch_bounds__(64) void shapes_kernel(const ShapesParams p) {
 
     for (int i = lane; i < (k + 1) * nb; i += 64) hist[i] = 0;
     tab[lane] = 0;
-    const int8_t *a = p.a0 + (size_t)c * p.npad;
+    const int8_t *a = w.a0 + (size_t)c * w.npad;
     for (int u = lane; u < n; u += 64) cur[u] = (int8_t)((int)a[u] & 31);
     __syncthreads();
     // the window-start areas and perimeters by LDS adds: a node brings its exterior length and
@@ -101,7 +99,7 @@ __global__ __launch_bounds__(64) void shapes_kernel(const ShapesParams p) {
     }
     __syncthreads();
 
-    const int64_t t0 = p.t0[cl];
+    const int64_t t0 = w.t0[cl];
     // lane d < k: district d
     int32_t A = lane < k ? tab[lane & 31] : 0;
     int32_t P = lane < k ? tab[32 + (lane & 31)] : 0;
@@ -120,8 +118,8 @@ __global__ __launch_bounds__(64) void shapes_kernel(const ShapesParams p) {
         mbin = score_bin(eq, qmin);
     }
 
-    const ulonglong2 *ev = (const ulonglong2 *)(p.events + (size_t)c * p.ev_cap);
-    const int64_t ne = p.ev_len[cl] < p.ev_cap ? p.ev_len[cl] : p.ev_cap;
+    const ulonglong2 *ev = (const ulonglong2 *)(w.events + (size_t)c * w.ev_cap);
+    const int64_t ne = w.ev_len[cl] < w.ev_cap ? w.ev_len[cl] : w.ev_cap;
     // this lane's event of log index idx: its node (-1: none) and target
     auto decode = [&](const ulonglong2 &e, int64_t idx, int &v, int &tg) {
         v = (int)(e.y & 0xffffu);
@@ -226,7 +224,7 @@ __global__ __launch_bounds__(64) void shapes_kernel(const ShapesParams p) {
     }
 
     // the window's end: every integral takes its last segment
-    const int64_t t1 = p.t_end[cl];
+    const int64_t t1 = w.t_end[cl];
     psum += (int64_t)P * (t1 - t_last);
     qsum += (int64_t)Q * (t1 - t_last);
     min_sum += (int64_t)qmin * (t1 - qmin_t);
@@ -252,17 +250,18 @@ __global__ __launch_bounds__(64) void shapes_kernel(const ShapesParams p) {
 
 template <int W>
 int launch_w(const ShapesParams &p, hipStream_t stream) {
-    const size_t lds = shapes_lds_bytes(p.npad, p.k, p.n_edges, W);
-    hipLaunchKernelGGL((shapes_kernel<W>), dim3((unsigned)p.nc), dim3(64), lds, stream, p);
+    const size_t lds = shapes_lds_bytes(p.log.npad, p.log.k, p.n_edges, W);
+    hipLaunchKernelGGL((shapes_kernel<W>), dim3((unsigned)p.log.nc), dim3(64), lds, stream, p);
     return (int)hipGetLastError();
 }
 
 }  // namespace
 
 int launch_shapes(const ShapesParams &p, void *stream) {
-    if (p.nc <= 0) return (int)hipSuccess;
-    if (p.k < 1 || p.k > 32 || p.n_edges < 0 || p.n_edges > kShapeMaxEdges || (p.width != 8 && p.width != 16) ||
-        p.n > p.npad || !shapes_fit_lds(p.npad, p.k, p.n_edges, p.width))
+    const LogWindow &w = p.log;
+    if (w.nc <= 0) return (int)hipSuccess;
+    if (w.k < 1 || w.k > 32 || p.n_edges < 0 || p.n_edges > kShapeMaxEdges || (p.width != 8 && p.width != 16) ||
+        w.n > w.npad || !shapes_fit_lds(w.npad, w.k, p.n_edges, p.width))
         return (int)hipErrorInvalidValue;
     return p.width == 8 ? launch_w<8>(p, (hipStream_t)stream) : launch_w<16>(p, (hipStream_t)stream);
 }

@@ -11,8 +11,8 @@
 #pragma once
 #include <stdint.h>
 
-#include "../../include/flipchain.h"
 #include "fc_philox.h"  // FC_HD
+#include "fc_replay.h"
 
 namespace fc {
 
@@ -28,14 +28,7 @@ FC_HD void election_rule(int64_t a, int64_t b, int32_t &win, int64_t &g) {
 
 // Kernel parameters (passed by value).  Output rows are per chain of the call, [nc] rows each.
 struct VotesParams {
-    const int8_t *a0;         // [n_chains * npad] assignment at the series window start
-    int32_t npad, n, k;
-    const fc_event *events;   // [n_chains * ev_cap]
-    int64_t ev_cap;
-    const int64_t *ev_len;    // [nc] events of chain c0 + i
-    const int64_t *t0;        // [nc] first yield of the window
-    const int64_t *t_end;     // [nc] last yield of the window + 1
-    int32_t c0, nc;
+    LogWindow log;            // the chains read and their window (fc_replay.h)
     const int32_t *cols;      // [n * NC] node columns, rows padded to the kernel's NC
     int32_t n_cols;
     int32_t n_el;

@@ -15,23 +15,14 @@
 // value * (t - t_since) when it changes, and once more at the window's end.
 #include <hip/hip_runtime.h>
 
+#include "fc_device.h"
 #include "fc_votes.h"
 
 namespace fc {
 namespace {
 
-__device__ __forceinline__ int32_t rl32(int32_t x, int l) { return __builtin_amdgcn_readlane(x, l); }
-__device__ __forceinline__ int64_t rl64(int64_t x, int l) {
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int32_t)(uint32_t)x, l);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int32_t)(uint32_t)((uint64_t)x >> 32), l);
-    return (int64_t)(((uint64_t)hi << 32) | lo);
-}
-
-__device__ __forceinline__ int64_t wave_sum64(int64_t v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor((long long)v, off);
-    return rl64(v, 0);
-}
+using dev::rl32;
+using dev::rl64;
 
 constexpr int kEdgeRegs = kVoteMaxEdges / 64;
 
@@ -55,14 +46,15 @@ __global__ __launch_bounds__(64) void votes_kernel(const VotesParams p) {
     constexpr int HE = kVoteMaxElections;  // histogram rows laid out in LDS (votes_hist_bytes)
     const int lane = (int)threadIdx.x;
     const int32_t cl = (int32_t)blockIdx.x;
-    const int32_t c = p.c0 + cl;
-    const int32_t k = p.k, n = p.n, n_edges = p.n_edges;
+    const LogWindow &w = p.log;
+    const int32_t c = w.c0 + cl;
+    const int32_t k = w.k, n = w.n, n_edges = p.n_edges;
     const int32_t nb = n_edges + 1;
     int64_t *hs = (int64_t *)smem;                  // [HE][k + 1] seats histograms
     int64_t *hg = hs + HE * (k + 1);                // [HE][nb] gap histograms
     int32_t *tl = (int32_t *)(hg + HE * nb);        // [32][kVoteMaxCols] initial tallies
     int8_t *lcur = (int8_t *)(tl + 32 * kVoteMaxCols);
-    int8_t *gcur = p.cur + (size_t)cl * p.npad;
+    int8_t *gcur = p.cur + (size_t)cl * w.npad;
     auto cur_get = [&](int u) -> int { return GC ? (int)gcur[u] : (int)lcur[u]; };
     auto cur_set = [&](int u, int d) {
         if (GC) gcur[u] = (int8_t)d; else lcur[u] = (int8_t)d;
@@ -72,7 +64,7 @@ __global__ __launch_bounds__(64) void votes_kernel(const VotesParams p) {
     for (int i = lane; i < 32 * kVoteMaxCols; i += 64) tl[i] = 0;
     __syncthreads();
     // the window-start assignment into cur, and its tallies by LDS adds
-    const int8_t *a = p.a0 + (size_t)c * p.npad;
+    const int8_t *a = w.a0 + (size_t)c * w.npad;
     for (int u = lane; u < n; u += 64) {
         const int d = (int)a[u] & 31;
         cur_set(u, d);
@@ -84,7 +76,7 @@ __global__ __launch_bounds__(64) void votes_kernel(const VotesParams p) {
     }
     __syncthreads();
 
-    const int64_t t0 = p.t0[cl];
+    const int64_t t0 = w.t0[cl];
     int32_t S[NC];
     int64_t ts[NC];
 #pragma unroll
@@ -119,7 +111,7 @@ __global__ __launch_bounds__(64) void votes_kernel(const VotesParams p) {
             }
             election_rule(ea[e], eb[e], win[e], g[e]);
             const int32_t s0 = __popcll(__ballot(win[e] != 0));
-            const int64_t g0 = wave_sum64(g[e]);
+            const int64_t g0 = rl64(dev::wave_sum64(g[e]), 0);  // wave-uniform
             const int32_t b0 = gap_bin(eq, n_edges, g0);
             if (lane == e) {
                 seats = s0;
@@ -129,8 +121,8 @@ __global__ __launch_bounds__(64) void votes_kernel(const VotesParams p) {
         }
     }
 
-    const ulonglong2 *ev = (const ulonglong2 *)(p.events + (size_t)c * p.ev_cap);
-    const int64_t ne = p.ev_len[cl] < p.ev_cap ? p.ev_len[cl] : p.ev_cap;
+    const ulonglong2 *ev = (const ulonglong2 *)(w.events + (size_t)c * w.ev_cap);
+    const int64_t ne = w.ev_len[cl] < w.ev_cap ? w.ev_len[cl] : w.ev_cap;
     // this lane's event of the next chunk, loaded one chunk ahead
     ulonglong2 nx = {0ull, 0ull};
     if (lane < ne) nx = ev[lane];
@@ -238,7 +230,7 @@ __global__ __launch_bounds__(64) void votes_kernel(const VotesParams p) {
     }
 
     // the window's end: every integral takes its last segment
-    const int64_t t1 = p.t_end[cl];
+    const int64_t t1 = w.t_end[cl];
     {
         const int64_t dt = t1 - t_last;
 #pragma unroll
@@ -275,12 +267,12 @@ __global__ __launch_bounds__(64) void votes_kernel(const VotesParams p) {
 
 template <int NC, int NEL>
 int launch_nc_ne(const VotesParams &p, bool global_cur, hipStream_t stream) {
-    const size_t hist = votes_hist_bytes(p.k, p.n_edges);
-    const dim3 grid((unsigned)p.nc), block(64);
+    const size_t hist = votes_hist_bytes(p.log.k, p.n_edges);
+    const dim3 grid((unsigned)p.log.nc), block(64);
     if (global_cur)
         hipLaunchKernelGGL((votes_kernel<NC, NEL, true>), grid, block, hist, stream, p);
     else
-        hipLaunchKernelGGL((votes_kernel<NC, NEL, false>), grid, block, hist + (((size_t)p.npad + 15) & ~(size_t)15),
+        hipLaunchKernelGGL((votes_kernel<NC, NEL, false>), grid, block, hist + (((size_t)p.log.npad + 15) & ~(size_t)15),
                            stream, p);
     return (int)hipGetLastError();
 }
@@ -302,10 +294,11 @@ int launch_nc(const VotesParams &p, bool global_cur, hipStream_t stream) {
 int votes_padded_cols(int32_t n_cols) { return n_cols <= 2 ? 2 : n_cols <= 4 ? 4 : 8; }
 
 int launch_votes(const VotesParams &p, bool global_cur, void *stream) {
-    if (p.nc <= 0) return (int)hipSuccess;
-    if (p.k < 1 || p.k > 32 || p.n_cols < 1 || p.n_cols > kVoteMaxCols || p.n_el < 0 || p.n_el > kVoteMaxElections ||
+    const LogWindow &w = p.log;
+    if (w.nc <= 0) return (int)hipSuccess;
+    if (w.k < 1 || w.k > 32 || p.n_cols < 1 || p.n_cols > kVoteMaxCols || p.n_el < 0 || p.n_el > kVoteMaxElections ||
         p.n_edges < 0 || p.n_edges > kVoteMaxEdges || (global_cur && !p.cur) ||
-        (!global_cur && !votes_cur_in_lds(p.npad, p.k, p.n_edges)))
+        (!global_cur && !votes_cur_in_lds(w.npad, w.k, p.n_edges)))
         return (int)hipErrorInvalidValue;
     switch (votes_padded_cols(p.n_cols)) {
     case 2: return launch_nc<2>(p, global_cur, (hipStream_t)stream);

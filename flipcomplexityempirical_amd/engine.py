@@ -535,6 +535,19 @@ class FlipRun:
         bounds = np.concatenate([[t0], ev["t"], [T + 1]]).astype(np.int64)
         return np.repeat(np.asarray(values)[:ev.size + 1], np.diff(bounds))
 
+    def _int64_series(self, entry: str, c0: int, nc: Optional[int], rows: Dict[str, Optional[tuple]]):
+        """Call the series entry point ``entry(handle, c0, nc, *outputs)``: ``rows`` gives, in the
+        entry point's order, each int64 output's shape per chain (None: not asked for, a null
+        pointer).  Returns the zero-filled ``[nc, *shape]`` outputs and ``yields``."""
+        nc = self.n_chains - c0 if nc is None else int(nc)
+        out = {key: np.zeros((max(nc, 0),) + shape, dtype=np.int64) for key, shape in rows.items()
+               if shape is not None}
+        check(getattr(_lib.load(), entry)(self.handle, int(c0), nc, *(_p(out.get(key), ctypes.c_int64) for key in rows)),
+              entry)
+        st = self.stats()
+        out["yields"] = (st["steps"] - st["series_t0"] + 1)[c0:c0 + nc].astype(np.int64)
+        return out
+
     # ---- election series (DESIGN.md §5c) ----------------------------------------------
     def set_elections(self, columns, elections: Sequence = (), gap_edges=None) -> "FlipRun":
         """Attach node vote columns (``fc_run_set_elections``): ``columns`` is ``[n, n_cols]``
@@ -568,23 +581,11 @@ class FlipRun:
         ``wins_sum`` ``[nc, n_el, k]``, ``gap_sum`` ``[nc, n_el]``, ``gap_hist``
         ``[nc, n_el, n_edges + 1]`` (only with ``gap_edges``) and ``yields`` ``[nc]``, the yields of
         each chain's window.  All int64."""
-        nc = self.n_chains - c0 if nc is None else int(nc)
         n_cols, n_el, n_edges = getattr(self, "_elections", (1, 0, 0))
         k = self.cfg.k
-        m = max(nc, 0)
-        out = {"tally_now": np.zeros((m, k, n_cols), dtype=np.int64),
-               "tally_sum": np.zeros((m, k, n_cols), dtype=np.int64),
-               "seats_hist": np.zeros((m, n_el, k + 1), dtype=np.int64),
-               "wins_sum": np.zeros((m, n_el, k), dtype=np.int64),
-               "gap_sum": np.zeros((m, n_el), dtype=np.int64)}
-        if n_edges:
-            out["gap_hist"] = np.zeros((m, n_el, n_edges + 1), dtype=np.int64)
-        check(_lib.load().fc_run_election_series(self.handle, int(c0), nc, *(
-            _p(out.get(key), ctypes.c_int64) for key in ("tally_now", "tally_sum", "seats_hist", "wins_sum",
-                                                         "gap_sum", "gap_hist"))), "fc_run_election_series")
-        st = self.stats()
-        out["yields"] = (st["steps"] - st["series_t0"] + 1)[c0:c0 + nc].astype(np.int64)
-        return out
+        return self._int64_series("fc_run_election_series", c0, nc, {
+            "tally_now": (k, n_cols), "tally_sum": (k, n_cols), "seats_hist": (n_el, k + 1), "wins_sum": (n_el, k),
+            "gap_sum": (n_el,), "gap_hist": (n_el, n_edges + 1) if n_edges else None})
 
     # ---- compactness series (DESIGN.md §5d) -------------------------------------------
     def set_shapes(self, area, edge_len, exterior=None, pp_edges=None) -> "FlipRun":
@@ -618,22 +619,11 @@ class FlipRun:
         ``pp_hist`` ``[nc, k, n_edges + 1]`` and ``pp_min_hist`` ``[nc, n_edges + 1]`` (only with
         ``pp_edges``) and ``yields`` ``[nc]``, the yields of each chain's window.  All int64; the
         Polsby-Popper score of a ``pp`` value ``Q`` is ``4 pi Q / 2**20``."""
-        nc = self.n_chains - c0 if nc is None else int(nc)
         n_edges = getattr(self, "_shape_edges", 0)
         k = self.cfg.k
-        m = max(nc, 0)
-        keys = ("area_now", "perim_now", "perim_sum", "pp_now", "pp_sum", "pp_min_sum", "pp_hist", "pp_min_hist")
-        out = {key: np.zeros((m, k), dtype=np.int64) for key in keys[:5]}
-        out["pp_min_sum"] = np.zeros(m, dtype=np.int64)
-        if n_edges:
-            out["pp_hist"] = np.zeros((m, k, n_edges + 1), dtype=np.int64)
-            out["pp_min_hist"] = np.zeros((m, n_edges + 1), dtype=np.int64)
-        check(_lib.load().fc_run_shape_series(self.handle, int(c0), nc,
-                                              *(_p(out.get(key), ctypes.c_int64) for key in keys)),
-              "fc_run_shape_series")
-        st = self.stats()
-        out["yields"] = (st["steps"] - st["series_t0"] + 1)[c0:c0 + nc].astype(np.int64)
-        return out
+        return self._int64_series("fc_run_shape_series", c0, nc, {
+            "area_now": (k,), "perim_now": (k,), "perim_sum": (k,), "pp_now": (k,), "pp_sum": (k,), "pp_min_sum": (),
+            "pp_hist": (k, n_edges + 1) if n_edges else None, "pp_min_hist": (n_edges + 1,) if n_edges else None})
 
     # ---- replica exchange (DESIGN.md "Replica exchange") ------------------------------
     def set_ladders(self, ladders: Sequence[Sequence[int]], hist: bool = False) -> "FlipRun":
