@@ -313,6 +313,7 @@ static fc::KParams flip_params(const fc_run *r, int64_t n_steps, int64_t max_dra
     k.seed_lo = (uint32_t)r->p.seed;
     k.seed_hi = (uint32_t)(r->p.seed >> 32);
     k.pop_lo = (int32_t)r->p.pop_lo;
+    k.pop_hi = (int32_t)r->p.pop_hi;
     k.n_steps = n_steps;
     k.max_draws = max_draws > 0 ? max_draws : 65536 * std::max<int64_t>(n_steps, 1);
     k.assign = r->d_assign;
@@ -320,7 +321,6 @@ static fc::KParams flip_params(const fc_run *r, int64_t n_steps, int64_t max_dra
     k.sc = r->d_sc;
     k.thresh = r->d_thresh;
     k.log1mp = r->d_log1mp;
-    k.pkeys = r->d_pkeys;
     k.labels = r->d_labels;
     k.diag = r->p.diag_mask;
     k.flags = r->p.flags;
@@ -529,7 +529,7 @@ int fc_run_steps(fc_run *r, int64_t n_steps, int64_t max_draws, void *hip_stream
             k.eta_parity = (int32_t)(r->n_flip_launches++ & 1);
             HIP_TRY(hipMemsetAsync(r->d_eta + k.eta_parity, 0, sizeof(uint32_t), s));
         }
-        const int e = r->p.k == 2 ? fc::launch_flip2(k, r->g.ring_max, s, r->kname, sizeof r->kname)
+        const int e = r->p.k == 2 ? fc::launch_flip2(k, r->d_pkeys, r->g.ring_max, s, r->kname, sizeof r->kname)
                                     : fc::launch_flipk(k, r->g.ring_max, s, r->kname, sizeof r->kname);
         if (e != 0) return fail(FC_ERR_HIP, std::string("flip kernel launch: ") + hipGetErrorString((hipError_t)e));
         if (k.tl_len) {  // the launch's logged tallies, applied and the logs emptied

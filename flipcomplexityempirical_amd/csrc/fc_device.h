@@ -615,10 +615,10 @@ __device__ __attribute__((noinline)) inline int64_t geom_wait_of(uint32_t x0, ui
 
 // Host: launch `kern` with `lds` bytes of dynamic LDS per workgroup (above 64 KB the kernel's
 // limit has to be raised first).  The caller reads hipGetLastError().
-template <typename P>
-inline void launch_lds(void (*kern)(P), dim3 grid, dim3 block, size_t lds, hipStream_t s, const P &p) {
+template <typename... P>
+inline void launch_lds(void (*kern)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t s, const P &...p) {
     if (lds > 65536) (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(kern, grid, block, lds, s, p);
+    hipLaunchKernelGGL(kern, grid, block, lds, s, p...);
 }
 
 }  // namespace fc

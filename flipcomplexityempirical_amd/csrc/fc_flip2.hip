@@ -51,8 +51,31 @@ using namespace dev;
 #ifndef FC_PRIO_EVERY_LOG2
 #define FC_PRIO_EVERY_LOG2 4  // profiles/r04p_prio_period_ab.txt: 55.0 ms against 55.4 every 4 batches, 56.3 every batch
 #endif
+// The key table's pointer (flip2_kernel's second argument) for one Philox call of a batch.  The
+// lean instances take the argument as it is, behind a barrier that keeps the 20 key words from
+// being loaded before the loop and held across it (they spilled).  The FULL instances have no
+// scalar registers to hold even the pointer across the loop (held, it cost 17 more SGPR spills
+// and with them 16 B of scratch in <8, *, true, false, false, false>): they read it again from
+// the kernel-argument segment, where it follows KParams, one scalar load per call.
+static_assert(sizeof(KParams) % 8 == 0, "flip2_kernel's second argument sits at sizeof(KParams)");
+template <bool FULL>
+__device__ __forceinline__ PhiloxKeys batch_keys(PhiloxKeys keys) {
+    typedef const unsigned char __attribute__((address_space(4))) *KernArg;
+    if constexpr (FULL) {
+        KernArg ka = (KernArg)__builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(ka));
+        return *(const PhiloxKeys __attribute__((address_space(4))) *)(ka + sizeof(KParams));
+    } else {
+        asm volatile("" : "+s"(keys));
+        return keys;
+    }
+}
+
+// keys: the run's Philox round-key table (fc_philox.h), an argument of its own after KParams:
+// with the pointer inside the struct the same loop ran slower (profiles/r09a_flip2_keyarg.txt),
+// and a longer KParams would move every other kernel's hidden arguments.
 template <int RMAX, int NSUB, bool FULL, bool SEARCH, bool XTRA, bool BAND>
-__global__ __launch_bounds__(256, (RMAX == 8 ? 4 : 1)) void flip2_kernel(KParams p) {
+__global__ __launch_bounds__(256, (RMAX == 8 ? 4 : 1)) void flip2_kernel(KParams p, PhiloxKeys keys) {
     static_assert(FULL || !XTRA, "XTRA is a FULL instance");
     // non-hit draws held per lane: the node stream's four words per Philox call, BAND's rounds
     constexpr int kRV = BAND ? NSUB : 4;
@@ -130,8 +153,12 @@ __global__ __launch_bounds__(256, (RMAX == 8 ? 4 : 1)) void flip2_kernel(KParams
     const bool want_wait = (p.diag & FC_DIAG_WAIT) != 0;
     const bool trace_on = XTRA && p.trace && c < p.trace_chains;
     // accepted states queued (wait_flush: their waits drawn, FULL: their tallies applied later)
-    // unless a trace or a replay tape needs the waits per batch
-    const bool defer = (want_wait || FULL) && !trace_on && !(XTRA && p.tape);
+    // unless a trace or a replay tape needs the waits per batch.  The lean node-stream instances
+    // (no trace, no tape) always queue, also with the waits off (wait_flush then draws none): a
+    // compile-time constant there, so they carry no per-batch form of the sums (10.31 -> 10.22 M
+    // instructions per wave and C2 launch, -0.4 ms; the lean BAND instances keep the run-time form:
+    // as a constant it cost them 16 B of scratch; profiles/r09a_flip2_keyarg.txt)
+    const bool defer = (!FULL && !BAND) || ((want_wait || FULL) && !trace_on && !(XTRA && p.tape));
 
     // per-lane accumulators, reduced once per launch
     int64_t acc_cut = 0, acc_nb = 0, acc_wait = 0, acc_cut2 = 0, acc_nb2 = 0;
@@ -285,7 +312,6 @@ __global__ __launch_bounds__(256, (RMAX == 8 ? 4 : 1)) void flip2_kernel(KParams
         misc[1] = (uint64_t)__float_as_uint(eta0);
     }
     compiler_fence();
-    const PhiloxKeys pkeys0 = (PhiloxKeys)(uintptr_t)p.pkeys;
     while (rem > 0) {
         // re-chosen every 2^FC_PRIO_EVERY_LOG2 batches (it moves slowly; scheduling only)
         const bool every = ((prio += 4) & (((1 << FC_PRIO_EVERY_LOG2) - 1) << 2)) == 0;
@@ -346,8 +372,7 @@ __global__ __launch_bounds__(256, (RMAX == 8 ? 4 : 1)) void flip2_kernel(KParams
                 }
             } else {
                 // (the round keys: read here, in every batch -- held across the loop they spilled)
-                PhiloxKeys pk = pkeys0;
-                asm volatile("" : "+s"(pk));
+                const PhiloxKeys pk = batch_keys<FULL>(keys);
                 const Words4 w = philox4x32_10_keys((uint32_t)q, (uint32_t)(q >> 32), chain_gid, 3u, pk);
                 nw[0] = w.x0;
                 nw[1] = w.x1;
@@ -465,20 +490,23 @@ __global__ __launch_bounds__(256, (RMAX == 8 ? 4 : 1)) void flip2_kernel(KParams
             w2 = slot[128 + lane];
         } else {
             // node stream: words 1-2 of the draw's own Philox call (ctr = draw, chain, purpose 0),
-            // made for the hits only; kept in the slots for the re-evaluations
+            // made for the hits only; kept for the re-evaluations: in the slots by the FULL
+            // instances, in these two registers by the lean ones, which have the room (two LDS
+            // stores per batch and two reads per re-evaluation fewer; profiles/r09a_flip2_keyarg.txt)
             if (XTRA && p.tape) {
                 const uint32_t *t = p.tape + ((size_t)c * (size_t)p.tape_draws + (has ? d : draw)) * 6;
                 w1 = t[1];
                 w2 = t[2];
             } else {
-                PhiloxKeys pk = pkeys0;
-                asm volatile("" : "+s"(pk));
+                const PhiloxKeys pk = batch_keys<FULL>(keys);
                 const Words4 g = philox4x32_10_keys((uint32_t)d, (uint32_t)(d >> 32), chain_gid, 0u, pk);
                 w1 = g.x1;
                 w2 = g.x2;
             }
-            slot[64 + lane] = w1;
-            slot[128 + lane] = w2;
+            if constexpr (FULL) {
+                slot[64 + lane] = w1;
+                slot[128 + lane] = w2;
+            }
         }
         const NodeRec<RMAX> rec = G[v];
         int av = a[v];
@@ -564,7 +592,7 @@ __global__ __launch_bounds__(256, (RMAX == 8 ? 4 : 1)) void flip2_kernel(KParams
             compiler_fence();
             if (has && lane >= from) {
                 const uint32_t lkl = slot[256 + lane];
-                const uint32_t w1r = slot[64 + lane], w2r = slot[128 + lane];
+                const uint32_t w1r = (!FULL && !BAND) ? w1 : slot[64 + lane], w2r = (!FULL && !BAND) ? w2 : slot[128 + lane];
                 if (vfx < 0) {
                     av = a[v];
                     uint32_t i1 = 0;
@@ -1316,7 +1344,7 @@ __global__ __launch_bounds__(256, (RMAX == 8 ? 4 : 1)) void flip2_kernel(KParams
     }
 }
 
-int launch_flip2(const KParams &p, int ring_max, void *stream, char *name, size_t name_cap) {
+int launch_flip2(const KParams &p, const uint32_t *pkeys, int ring_max, void *stream, char *name, size_t name_cap) {
     // one chain (wave) per workgroup: the dispatcher then deals consecutive chains, whose
     // bases differ, round-robin over the XCDs, CUs and SIMDs, and the short-boundary chains
     // that set the launch time spread more evenly over the SIMDs than four to a workgroup
@@ -1327,6 +1355,7 @@ int launch_flip2(const KParams &p, int ring_max, void *stream, char *name, size_
     const size_t lds = (size_t)p.chain_lds_bytes * wpb;
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid(blocks), block(kWave * wpb);
+    const PhiloxKeys keys = (PhiloxKeys)(uintptr_t)pkeys;  // the run's own table (fc_run_create)
     // FULL: replay tapes, traces, event logs, histograms, per-node/per-edge tallies or a
     // hitting-time window; the lean instance keeps its registers for the hot loop.
     const bool full = p.tape || p.trace || (p.diag & ~(uint32_t)FC_DIAG_WAIT) || p.hit_lo <= p.hit_hi || p.variant;
@@ -1339,7 +1368,7 @@ int launch_flip2(const KParams &p, int ring_max, void *stream, char *name, size_
         if (name)                                                                                           \
             snprintf(name, name_cap, "fc::flip2_kernel<%d, %d, %s, %s, %s, %s>", R, S, F ? "true" : "false", \
                      X ? "true" : "false", Y ? "true" : "false", B ? "true" : "false");                    \
-        launch_lds(flip2_kernel<R, S, F, X, Y, B>, grid, block, lds, s, p);                                 \
+        launch_lds(flip2_kernel<R, S, F, X, Y, B>, grid, block, lds, s, p, keys);                           \
     } while (0)
 #define FC_LAUNCH2(R, S, F, X, Y)                        \
     do {                                                 \

@@ -94,11 +94,7 @@ struct KParams {
     uint32_t lemire_thresh;     // 2^32 mod n
     uint32_t chain_id_offset;
     uint32_t seed_lo, seed_hi;
-    int32_t pop_lo;             // (unused by the kernels: each chain's bounds are in ChainScalars)
-    // k = 2: [kPhiloxKeyWords] the seed's Philox round keys (fc_philox.h).  It takes the word of
-    // the former pop_hi (as unused as pop_lo) and the padding before n_steps, so every other
-    // field keeps its offset and the other kernels' code is unchanged
-    const uint32_t *pkeys;
+    int32_t pop_lo, pop_hi;     // (unused by the kernels: each chain's bounds are in ChainScalars)
     int64_t n_steps;            // steps to advance per chain in this launch
     int64_t max_draws;          // per chain per launch
     int8_t *assign;             // [n_chains * n]
@@ -178,7 +174,6 @@ struct KParams {
     int32_t band_step0;         // largest power of two below `words` (rank search over the words)
     uint64_t *sbits;            // [n_chains * words]
 };
-static_assert(offsetof(KParams, pkeys) == 64 && offsetof(KParams, n_steps) == 72, "KParams: pkeys fills pop_hi's slot");
 
 // chain dealing: SIMD keys are XCC_ID[2:0] . HW_ID[15:4] (SIMD, pipe, CU, SH, SE)
 constexpr int kDealKeys = 1 << 15;
@@ -224,7 +219,10 @@ int launch_recom(const RecomParams &p, int ring_max, void *stream, char *name, s
 // Launch wrappers.  Return a hipError_t as int.
 // `name` (may be null) receives the launched instance, spelled as rocprofv3 reports it.
 int launch_flipk(const KParams &p, int ring_max, void *stream, char *name, size_t name_cap);  // k > 2 (fc_kernels.hip)
-int launch_flip2(const KParams &p, int ring_max, void *stream, char *name, size_t name_cap);  // k = 2 (fc_flip2.hip)
+// k = 2 (fc_flip2.hip).  pkeys: [kPhiloxKeyWords] the seed's Philox round keys (fc_philox.h), in
+// device memory; the kernel takes the pointer as an argument of its own after KParams, so the
+// struct (and with it every other kernel's argument layout) does not carry it
+int launch_flip2(const KParams &p, const uint32_t *pkeys, int ring_max, void *stream, char *name, size_t name_cap);
 // k = 2 full diagnostics: apply every chain's tally log (KParams tl_*) to the per-chain
 // histograms / per-node / per-edge arrays and reset the logs (fc_tally.hip)
 int launch_tally_reduce(const KParams &p, int ring_max, void *stream);

@@ -62,7 +62,10 @@ inline void philox_round_keys(uint32_t k0, uint32_t k1, uint32_t *out) {
 }
 #if defined(__HIPCC__) || defined(__HIP__)
 typedef const uint32_t __attribute__((address_space(4))) *PhiloxKeys;  // constant memory: scalar loads
-__device__ __forceinline__ Words4 philox4x32_10_keys(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, PhiloxKeys kp) {
+#endif
+// KP: PhiloxKeys in the kernel; a plain pointer on the host (tests/native/philox_keys_check.cpp)
+template <typename KP>
+FC_HD Words4 philox4x32_10_keys(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, KP kp) {
     uint32_t K[kPhiloxKeyWords];
 #pragma unroll
     for (int i = 0; i < kPhiloxKeyWords; ++i) K[i] = kp[i];
@@ -82,7 +85,6 @@ __device__ __forceinline__ Words4 philox4x32_10_keys(uint32_t c0, uint32_t c1, u
     }
     return Words4{c0, c1, c2, c3};
 }
-#endif
 
 // 53-bit mantissa of CPython random() / numpy random_sample() from two words.
 FC_HD uint64_t mant53(uint32_t a, uint32_t b) { return ((uint64_t)(a >> 5) << 26) | (uint64_t)(b >> 6); }
