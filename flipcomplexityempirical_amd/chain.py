@@ -178,6 +178,44 @@ class Compactness:
         return area, np.asarray(lens, dtype=np.int64), ext
 
 
+class LocalitySplits:
+    """How a partition cuts through the localities given by the node attribute ``attr`` (counties,
+    municipalities) -- gerrychain's ``county_splits`` updater [gc-0.2] without the connected-pieces
+    search.  Called on a partition it returns ``{locality: {"parts", "split", "districts"}}`` (the
+    number of parts the locality meets, whether that is two or more, and those parts, sorted) plus
+    the two plan-level keys ``"num_split"`` (split localities) and ``"excess"`` (the sum of
+    ``parts - 1``).  As an updater of a chain's initial state it makes :meth:`MarkovChain.run`
+    replay the splits over every yield on the device (``ChainResult.splits``)."""
+
+    def __init__(self, attr: str = "county"):
+        self.attr = attr
+
+    def _label(self, graph, nd):
+        if self.attr not in graph.nodes[nd]:
+            raise ValueError(f"node {nd!r} has no attribute {self.attr!r}")
+        return graph.nodes[nd][self.attr]
+
+    def __call__(self, partition) -> Dict[Any, Any]:
+        g, a = partition.graph, partition.assignment
+        met: Dict[Any, set] = {}
+        for nd, p in a.items():
+            met.setdefault(self._label(g, nd), set()).add(p)
+        out: Dict[Any, Any] = {loc: {"parts": len(ps), "split": len(ps) >= 2, "districts": sorted(ps)}
+                               for loc, ps in met.items()}
+        out["num_split"] = sum(1 for ps in met.values() if len(ps) >= 2)
+        out["excess"] = sum(len(ps) - 1 for ps in met.values())
+        return out
+
+    def arrays(self, graph, spec: GraphSpec):
+        """``(labels, node_loc)``: the distinct attribute values in ascending order and, in the
+        canonical node order of ``spec``, each node's index into them (int32, for
+        ``FlipRun.set_localities``); ValueError for a node without the attribute."""
+        vals = [self._label(graph, nd) for nd in spec.nodes]
+        labels = sorted(set(vals))
+        lut = {x: i for i, x in enumerate(labels)}
+        return labels, np.asarray([lut[x] for x in vals], dtype=np.int32)
+
+
 def cut_edges(partition):
     """``gerrychain.updaters.cut_edges``: edges (sorted tuples) whose ends are in different parts."""
     a = partition.assignment
@@ -853,7 +891,9 @@ class MarkovChain:
         elections = {key: u for key, u in self.initial_state.updaters.items() if isinstance(u, Election)}
         # the (first) Compactness updater likewise: district shapes over every yield (§5d)
         shapes = next((u for u in self.initial_state.updaters.values() if isinstance(u, Compactness)), None)
-        log = series or bool(elections) or shapes is not None
+        # ... and the (first) LocalitySplits updater: locality splits over every yield (§5e)
+        splits = next((u for u in self.initial_state.updaters.values() if isinstance(u, LocalitySplits)), None)
+        log = series or bool(elections) or shapes is not None or splits is not None
         if log:
             diag |= _lib.FC_DIAG_SERIES
         if corrected:
@@ -870,6 +910,9 @@ class MarkovChain:
         if shapes is not None:
             area, lens, ext = shapes.arrays(self.initial_state.graph, self.cspec.spec, self.edges)
             run.set_shapes(area, lens, ext)
+        if splits is not None:
+            loc_labels, node_loc = splits.arrays(self.initial_state.graph, self.cspec.spec)
+            run.set_localities(node_loc)
         if self.total_steps > 1:
             run.steps(self.total_steps - 1)
         res = ChainResult.from_run(self, run, 0)
@@ -877,6 +920,12 @@ class MarkovChain:
             ss = run.shape_series(0, 1)
             res.shapes = {key: ss[key][0].copy() for key in ("area_now", "perim_now", "perim_sum", "pp_now", "pp_sum")}
             res.shapes.update(pp_min_sum=int(ss["pp_min_sum"][0]), yields=int(ss["yields"][0]))
+        if splits is not None:
+            ss = run.split_series(0, 1)
+            res.splits = {key: ss[key][0].copy() for key in ("cells_now", "split_sum", "parts_sum", "dlocs_sum",
+                                                             "splits_hist", "excess_hist", "parts_now", "dlocs_now")}
+            res.splits.update({key: int(ss[key][0]) for key in ("sq_sum", "splits_now", "excess_now", "sq_now", "yields")})
+            res.splits.update(x_max=ss["x_max"], localities=loc_labels)
         if elections:
             es = run.election_series(0, 1)
             res.elections = {}
@@ -954,6 +1003,12 @@ class ChainResult:
     # perim_now, perim_sum, pp_now, pp_sum [k] (parts in label order; pp in units of
     # Q = floor(2^20 A / P^2)), pp_min_sum, yields
     shapes: Optional[Dict[str, Any]] = None
+    # from the LocalitySplits updater of the initial state, over all yields:
+    # localities (the attribute's values, ascending: the rows' order), cells_now [n_loc, k],
+    # split_sum, parts_sum, parts_now [n_loc], dlocs_sum, dlocs_now [k] (parts in label order),
+    # splits_hist [n_loc + 1], excess_hist [min(x_max, 1023) + 1], sq_sum, splits_now, excess_now,
+    # sq_now, x_max, yields
+    splits: Optional[Dict[str, Any]] = None
 
     def heatmaps(self, shape=(40, 40), offset=(0, 0)) -> Dict[str, np.ndarray]:
         """The driver's ``A2`` arrays (``grid_chain_sec11.py:431-528``): ``A2[n[0], n[1]]``

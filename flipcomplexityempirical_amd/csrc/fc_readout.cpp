@@ -736,6 +736,104 @@ int fc_run_shape_series(fc_run *r, int32_t c0, int32_t nc, int64_t *area_now, in
     return out.fetch(r, {area_now, perim_now, perim_sum, pp_now, pp_sum, pp_min_sum, pp_hist, pp_min_hist});
 }
 
+// ---- locality-splits series (fc_splits.h, fc_splits.hip) ------------------------
+
+int fc_splits_eval(int32_t n_loc, int32_t k, const int64_t *cells, int64_t *splits, int64_t *excess, int64_t *sq) {
+    if (!cells) return fail(FC_ERR_ARG, "fc_splits_eval: null argument");
+    if (n_loc < 1) return fail(FC_ERR_ARG, "fc_splits_eval: n_loc must be at least 1");
+    if (k < 1 || k > fc::kMaxKGeneral) return fail(FC_ERR_ARG, "fc_splits_eval: k must be 1..32");
+    int64_t s = 0, x = 0, q = 0;
+    for (int32_t c = 0; c < n_loc; ++c) {
+        // the locality's nodes enter its cells one by one, by the rule the device applies per flip
+        int32_t parts = 0, split = 0;
+        for (int32_t d = 0; d < k; ++d) {
+            const int64_t cnt = cells[(size_t)c * k + d];
+            if (cnt < 0 || cnt > fc::kSplitCellMax)
+                return fail(FC_ERR_ARG, "fc_splits_eval: cells must be in 0 .. 65535");
+            for (int32_t i = 0; i < (int32_t)cnt; ++i) {
+                int32_t dp, ds;
+                int64_t dq;
+                fc::split_rule(i, +1, parts, dp, ds, dq);
+                parts += dp;
+                split += ds;
+                q += dq;
+            }
+        }
+        if (parts == 0) return fail(FC_ERR_ARG, "fc_splits_eval: locality " + std::to_string(c) + " has no node");
+        s += split;
+        x += parts - 1;
+    }
+    if (splits) *splits = s;
+    if (excess) *excess = x;
+    if (sq) *sq = q;
+    return FC_OK;
+}
+
+int fc_run_set_localities(fc_run *r, int32_t n_loc, const int32_t *node_loc) {
+    if (!r || !node_loc) return fail(FC_ERR_ARG, "fc_run_set_localities: null argument");
+    if (r->p.proposal == FC_PROPOSE_RECOM)
+        return fail(FC_ERR_UNSUPPORTED,
+                    "fc_run_set_localities: the locality-splits series replays the flip log (not ReCom)");
+    if (!r->d_events) return fail(FC_ERR_ARG, "fc_run_set_localities: FC_DIAG_SERIES not enabled");
+    const int32_t n = r->g.n, k = r->p.k;
+    if (n_loc < 1 || n_loc > n) return fail(FC_ERR_ARG, "fc_run_set_localities: n_loc must be 1..n");
+    std::vector<int32_t> size(n_loc, 0);
+    for (int32_t u = 0; u < n; ++u) {
+        if (node_loc[u] < 0 || node_loc[u] >= n_loc)
+            return fail(FC_ERR_ARG, "fc_run_set_localities: label of node " + std::to_string(u) + " out of range");
+        ++size[node_loc[u]];
+    }
+    int64_t x_max = -(int64_t)n_loc;
+    for (int32_t c = 0; c < n_loc; ++c) {
+        if (size[c] == 0) return fail(FC_ERR_ARG, "fc_run_set_localities: label " + std::to_string(c) + " is unused");
+        x_max += std::min(size[c], k);
+    }
+    const int32_t x_top = (int32_t)std::min<int64_t>(x_max, fc::kSplitMaxExcess);
+    if (!fc::splits_fit_lds(r->npad, k, n_loc, x_top))
+        return fail(FC_ERR_UNSUPPORTED,
+                    "fc_run_set_localities: a chain's image (" +
+                        std::to_string(fc::splits_lds_bytes(r->npad, k, n_loc, x_top)) +
+                        " bytes: assignment, cell table, integrals, histograms) does not fit 48 KB of LDS");
+    if (int rc = fc_run_sync(r)) return rc;  // a reader of the previous table may still run
+    r->sp_n_loc = 0;
+    if (int rc = r->d_sp_loc.upload(node_loc, (size_t)n)) return rc;
+    r->sp_x_max = (int32_t)x_max;
+    r->sp_n_loc = n_loc;
+    return FC_OK;
+}
+
+int fc_run_split_series(fc_run *r, int32_t c0, int32_t nc, int64_t *cells_now, int64_t *split_sum, int64_t *parts_sum,
+                        int64_t *dlocs_sum, int64_t *sq_sum, int64_t *splits_hist, int64_t *excess_hist) {
+    if (!r) return fail(FC_ERR_ARG, "fc_run_split_series: null run");
+    if (int rc = check_series_call(r, "fc_run_split_series", c0, nc,
+                                   {"the locality-splits series", r->sp_n_loc ? nullptr : "fc_run_set_localities"}))
+        return rc;
+    if (nc == 0) return FC_OK;
+    SeriesCall s;
+    if (int rc = open_window(r, "fc_run_split_series", c0, nc, true, s)) return rc;
+    const int32_t k = r->p.k, L = r->sp_n_loc;
+    const int32_t x_top = std::min(r->sp_x_max, fc::kSplitMaxExcess);
+    const size_t cn = (size_t)nc;
+    OutPack out;
+    if (int rc = out.reserve(r, {cn * L * k, cn * L, cn * L, cn * k, cn, cn * ((size_t)L + 1), cn * ((size_t)x_top + 1)}))
+        return rc;
+    fc::SplitsParams sp{};
+    sp.log = s.log;
+    sp.node_loc = r->d_sp_loc;
+    sp.n_loc = L;
+    sp.x_top = x_top;
+    sp.cells_now = out.at(0);
+    sp.split_sum = out.at(1);
+    sp.parts_sum = out.at(2);
+    sp.dlocs_sum = out.at(3);
+    sp.sq_sum = out.at(4);
+    sp.splits_hist = out.at(5);
+    sp.excess_hist = out.at(6);
+    const int e = fc::launch_splits(sp, r->stream);
+    if (e) return fail(FC_ERR_HIP, std::string("locality-splits series: ") + hipGetErrorString((hipError_t)e));
+    return out.fetch(r, {cells_now, split_sum, parts_sum, dlocs_sum, sq_sum, splits_hist, excess_hist});
+}
+
 int fc_run_read_hist(fc_run *r, int64_t *cut_hist, int64_t *nb_hist) {
     if (!r || !cut_hist || !nb_hist) return fail(FC_ERR_ARG, "fc_run_read_hist: null argument");
     if (!r->d_cut_hist) return fail(FC_ERR_ARG, "fc_run_read_hist: FC_DIAG_HIST not enabled");

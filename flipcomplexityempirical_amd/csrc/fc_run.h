@@ -12,6 +12,7 @@
 #include "fc_ladder.h"
 #include "fc_plan.h"
 #include "fc_shapes.h"
+#include "fc_splits.h"
 #include "fc_votes.h"
 
 namespace fc {
@@ -170,6 +171,9 @@ struct fc_run : fc::RunShape {
     DevBuf<fc::ShapeSlot> d_sh_rows;   // [n * sh_width] neighbour rows
     DevBuf<fc::ShapeNode> d_sh_nodes;  // [n]
     DevBuf<int64_t> d_sh_edges;   // [sh_n_edges]
+    // locality-splits series (fc_run_set_localities; fc_splits.h, fc_splits.hip).  sp_n_loc 0: not set
+    int32_t sp_n_loc = 0, sp_x_max = 0;
+    DevBuf<int32_t> d_sp_loc;     // [n] node labels
     char kname[96] = {0};       // last launched flip-kernel instance
     // replica exchange (fc_run_set_ladders; fc_ladder.h, fc_exchange.hip).  Slots are flat: ladder
     // l's rung r is slot lad_off[l] + r

@@ -625,6 +625,45 @@ class FlipRun:
             "area_now": (k,), "perim_now": (k,), "perim_sum": (k,), "pp_now": (k,), "pp_sum": (k,), "pp_min_sum": (),
             "pp_hist": (k, n_edges + 1) if n_edges else None, "pp_min_hist": (n_edges + 1,) if n_edges else None})
 
+    # ---- locality-splits series ---------------------------------------
+    def set_localities(self, node_loc) -> "FlipRun":
+        """Attach a node labelling (``fc_run_set_localities``): ``node_loc`` ``[n]`` integer labels
+        ``0 .. n_loc - 1`` in canonical node order (counties, municipalities), every label used.
+        Callable again to replace it; a restored run needs it again."""
+        loc = np.asarray(node_loc)
+        if loc.shape != (self.graph.n,) or not np.issubdtype(loc.dtype, np.integer):
+            raise ValueError(f"node_loc must be {self.graph.n} integers")
+        if loc.size and (loc.min() < -2 ** 31 or loc.max() > 2 ** 31 - 2):
+            raise ValueError("node_loc must hold int32 labels")  # (the library checks the rest)
+        loc = np.ascontiguousarray(loc, dtype=np.int32)
+        n_loc = int(loc.max()) + 1 if loc.size else 0
+        check(_lib.load().fc_run_set_localities(self.handle, n_loc, _p(loc, ctypes.c_int32)), "fc_run_set_localities")
+        sizes = np.bincount(loc, minlength=n_loc)
+        self._localities = (n_loc, int(np.minimum(sizes, self.cfg.k).sum()) - n_loc)
+        return self
+
+    def split_series(self, c0: int = 0, nc: Optional[int] = None) -> Dict[str, np.ndarray]:
+        """Locality splits of chains ``c0 .. c0 + nc - 1`` over the series window, replayed on the
+        device from the flip log (``fc_run_split_series``; include/flipchain.h): ``cells_now``
+        ``[nc, n_loc, k]``, ``split_sum`` / ``parts_sum`` ``[nc, n_loc]``, ``dlocs_sum`` ``[nc, k]``,
+        ``sq_sum`` ``[nc]``, ``splits_hist`` ``[nc, n_loc + 1]``, ``excess_hist`` ``[nc, X + 1]``
+        (``X = min(x_max, 1023)``) and ``yields`` ``[nc]``, all int64; and, derived from ``cells_now``
+        on the host, ``parts_now`` ``[nc, n_loc]``, ``splits_now`` / ``excess_now`` / ``sq_now``
+        ``[nc]``, ``dlocs_now`` ``[nc, k]``, with ``x_max`` (an int) the largest possible excess."""
+        n_loc, x_max = getattr(self, "_localities", (1, 0))
+        k = self.cfg.k
+        out = self._int64_series("fc_run_split_series", c0, nc, {
+            "cells_now": (n_loc, k), "split_sum": (n_loc,), "parts_sum": (n_loc,), "dlocs_sum": (k,), "sq_sum": (),
+            "splits_hist": (n_loc + 1,), "excess_hist": (min(x_max, 1023) + 1,)})
+        occ = out["cells_now"] > 0
+        out["parts_now"] = occ.sum(axis=2).astype(np.int64)
+        out["splits_now"] = (out["parts_now"] >= 2).sum(axis=1).astype(np.int64)
+        out["excess_now"] = (out["parts_now"] - 1).sum(axis=1).astype(np.int64)
+        out["sq_now"] = (out["cells_now"] ** 2).sum(axis=(1, 2)).astype(np.int64)
+        out["dlocs_now"] = occ.sum(axis=1).astype(np.int64)
+        out["x_max"] = x_max
+        return out
+
     # ---- replica exchange (DESIGN.md "Replica exchange") ------------------------------
     def set_ladders(self, ladders: Sequence[Sequence[int]], hist: bool = False) -> "FlipRun":
         """``ladders``: lists of local chain indices, rung 0 first (``fc_run_set_ladders``; once

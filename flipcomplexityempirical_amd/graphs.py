@@ -274,6 +274,23 @@ def unit_square_shapes(spec: GraphSpec):
     return (np.ones(spec.n, dtype=np.int32), np.ones(spec.n_edges, dtype=np.int32), (4 - deg).astype(np.int32))
 
 
+def block_localities(spec: GraphSpec, bx: int, by: int) -> np.ndarray:
+    """Node labels ``[n]`` (int32, for ``FlipRun.set_localities``) of a lattice whose nodes are
+    integer ``(x, y)`` pairs (``grid_graph``, sec11): node ``(x, y)`` lies in block
+    ``(x // bx, y // by)``, and the blocks that hold a node are numbered densely in ascending
+    order.  ValueError for other node labels or a block side below 1."""
+    if int(bx) != bx or int(by) != by or bx < 1 or by < 1:
+        raise ValueError("block_localities: block sides must be integers >= 1")
+    blocks = []
+    for nd in spec.nodes:
+        if not (isinstance(nd, tuple) and len(nd) == 2 and
+                all(isinstance(x, (int, np.integer)) and not isinstance(x, bool) for x in nd)):
+            raise ValueError(f"block_localities: node {nd!r} is not an integer (x, y) pair")
+        blocks.append((int(nd[0]) // int(bx), int(nd[1]) // int(by)))
+    dense = {b: i for i, b in enumerate(sorted(set(blocks)))}
+    return np.asarray([dense[b] for b in blocks], dtype=np.int32)
+
+
 def threshold_plan(nodes: Sequence, axis: int, cut: float) -> Dict:
     """±1 plan by ``node[axis] >= cut`` (C1: 10x10 grid, ``x[0] >= 5``)."""
     return {n: (1 if n[axis] >= cut else -1) for n in nodes}

@@ -474,6 +474,60 @@ int fc_run_shape_series(fc_run *r, int32_t c0, int32_t nc,
 /* The score of one district, by the code the device runs: *q = Q(area, perim) as above.
  * FC_ERR_ARG for values below 0 or above 2^31 - 1.  Pure host function. */
 int fc_shape_score(int64_t area, int64_t perim, int64_t *q);
+/* ---- locality-splits series: how the sampled plans cut through administrative units
+ * (gerrychain's county_splits updater and the split / pieces counts reported beside an ensemble),
+ * by a device replay of the flip log against a node labelling.  Flip runs with
+ * FC_DIAG_SERIES, any k.  Input, per run, not trajectory state:
+ *   node_loc[n]  int32 labels in [0, n_loc), 1 <= n_loc <= n, every label used by at least one
+ *                node.  One labelling per run; fc_run_set_localities is callable again to replace
+ *                it (municipalities after counties: a second set + read over the same window).
+ * Over the window's yields t = series_t0 .. steps, with a_t the assignment at yield t (it holds
+ * from an event's t to the next event's):
+ *   cells_t[c][d] = number of nodes u with node_loc[u] = c and a_t(u) = d;
+ *   parts_t(c)    = number of d with cells_t[c][d] > 0 (at least 1);
+ *   locality c is split iff parts_t(c) >= 2;   splits_t = number of split localities;
+ *   excess_t      = sum_c (parts_t(c) - 1);
+ *   sq_t          = sum_{c,d} cells_t[c][d]^2: the numerator of the Simpson-type preservation
+ *                   index; divided by sum_c |c|^2 it is 1 when no locality is split;
+ *   dlocs_t[d]    = number of localities district d meets;
+ *   x_max         = sum_c min(|c|, k) - n_loc, the largest possible excess; X = min(x_max, 1023).
+ * Outputs per chain, all int64:
+ *   cells_now[c][d]  = cells at the current yield (parts, splits, excess, sq and dlocs "now"
+ *                      follow from it on the host);
+ *   split_sum[c]     = yields in which locality c is split;   parts_sum[c] = sum_t parts_t(c);
+ *   dlocs_sum[d]     = sum_t dlocs_t[d];                      sq_sum = sum_t sq_t;
+ *   splits_hist[s]   = yields with splits_t = s, s = 0..n_loc;
+ *   excess_hist[x]   = yields with min(excess_t, X) = x, x = 0..X: the top bin collects every
+ *                      larger excess.
+ * All exact integers; both histogram rows sum to the window's yields.  FC_DIAG_SERIES limits n to
+ * 65,535, so a cell fits 16 bits and sq_t < 2^32; with fewer than 2^30 window yields (checked)
+ * nothing overflows int64.
+ *
+ * fc_run_set_localities validates and uploads the labels.  Checkpoint blobs do not hold them (and
+ * are byte for byte what they were), so a restored run needs fc_run_set_localities again.
+ * FC_ERR_ARG without FC_DIAG_SERIES, for n_loc < 1 or > n, a label out of range or an unused label;
+ * FC_ERR_UNSUPPORTED for ReCom runs (no flip log) and when a chain's image does not fit 48 KB of
+ * LDS: 8 (3 n_loc + X + 34) + 4 n_loc + 4 ceil(n_loc k / 2) + the assignment row (n padded to 16)
+ * bytes; n <= 16,384 with n_loc <= 256 and n_loc k <= 4,096 always fits.
+ * fc_run_split_series fills the outputs of chains [c0, c0 + nc) (any may be NULL to skip it) and
+ * synchronises.  FC_ERR_ARG without FC_DIAG_SERIES, before fc_run_set_localities, for a bad chain
+ * range, for a window of 2^30 yields or more, or when a chain's log overflowed event_cap;
+ * FC_ERR_UNSUPPORTED for ReCom runs.  Calls interleave freely with the election, compactness and
+ * frame series and with other chain ranges. */
+int fc_run_set_localities(fc_run *r, int32_t n_loc, const int32_t *node_loc);
+int fc_run_split_series(fc_run *r, int32_t c0, int32_t nc,
+                        int64_t *cells_now,                      /* [nc * n_loc * k]  */
+                        int64_t *split_sum, int64_t *parts_sum,  /* [nc * n_loc]      */
+                        int64_t *dlocs_sum,                      /* [nc * k]          */
+                        int64_t *sq_sum,                         /* [nc]              */
+                        int64_t *splits_hist,                    /* [nc * (n_loc+1)]  */
+                        int64_t *excess_hist);                   /* [nc * (X+1)]      */
+/* The per-yield aggregates of one cell table, by the rule the device applies per flip (every
+ * node entering its cell in turn): cells [n_loc * k], each 0 .. 65,535, every locality with at
+ * least one node, n_loc >= 1, 1 <= k <= 32 (FC_ERR_ARG otherwise); *splits, *excess, *sq as
+ * defined above.  Any output may be NULL.  Pure host function; its cost grows with the nodes. */
+int fc_splits_eval(int32_t n_loc, int32_t k, const int64_t *cells,
+                   int64_t *splits, int64_t *excess, int64_t *sq);
 /* Page-lock (pin) a caller's host buffer for faster device-to-host copies of the readers above
  * (hipHostRegister); unregister before freeing it. */
 int fc_host_register(void *ptr, int64_t bytes);
