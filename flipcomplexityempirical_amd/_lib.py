@@ -49,6 +49,7 @@ EXPORTED = [
     "fc_run_set_elections", "fc_run_election_series", "fc_election_eval",
     "fc_run_set_shapes", "fc_run_shape_series", "fc_shape_score",
     "fc_run_set_localities", "fc_run_split_series", "fc_splits_eval",
+    "fc_run_sample_plans", "fc_run_sample_plans_ms",
     "fc_run_destroy",
     "fc_device_count", "fc_device_pci_id", "fc_last_error", "fc_build_flags", "fc_build_id",
 ]
@@ -248,6 +249,8 @@ def load(build_if_missing: bool = True, allow_variant: bool = False):
     L.fc_run_set_localities.argtypes = [vp, i32, _P(i32)]
     L.fc_run_split_series.argtypes = [vp, i32, i32] + [_P(i64)] * 7
     L.fc_splits_eval.argtypes = [i32, i32, _P(i64), _P(i64), _P(i64), _P(i64)]
+    L.fc_run_sample_plans.argtypes = [vp, i32, i32, i32, _P(i64), _P(ctypes.c_int8)] + [_P(i64)] * 4
+    L.fc_run_sample_plans_ms.argtypes = [vp, _P(ctypes.c_float), _P(ctypes.c_float)]
     L.fc_device_pci_id.argtypes = [i32, ctypes.c_char_p, i32]
     L.fc_run_destroy.argtypes = [vp]
     L.fc_run_destroy.restype = None

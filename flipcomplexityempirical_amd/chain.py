@@ -703,7 +703,8 @@ class _AssignmentView(Mapping):
 
 class StateView:
     """A yielded chain state: ``part[key]`` for the reference's updaters, ``part.assignment``,
-    ``part.flips`` (stale on rejected steps, as in gerrychain), ``part.parent`` (None)."""
+    ``part.flips`` (stale on rejected steps, as in gerrychain), ``part.parent`` (None).  ``wait``
+    None (a sampled plan of ``ChainResult.sampled()``): the state carries no geometric wait."""
 
     def __init__(self, chain, a: np.ndarray, flips, wait: int, cut: int, nb: int, step: int):
         self._chain = chain
@@ -712,7 +713,7 @@ class StateView:
         self.parent = None
         self.graph = chain.initial_state.graph
         self.updaters = chain.initial_state.updaters
-        self._cache: Dict[str, Any] = {"geom": wait}
+        self._cache: Dict[str, Any] = {} if wait is None else {"geom": wait}
         self._cut, self._nb, self.step = cut, nb, step
         self.assignment = _AssignmentView(a, chain.cspec.spec, chain.cspec.labels)
 
@@ -865,7 +866,8 @@ class MarkovChain:
         run.close()
 
     # ---- fast path -------------------------------------------------------------------
-    def run(self, series: bool = True, frame: Optional[str] = "auto", corrected: bool = True) -> "ChainResult":
+    def run(self, series: bool = True, frame: Optional[str] = "auto", corrected: bool = True,
+            sample_every: Optional[int] = None) -> "ChainResult":
         """All ``total_steps`` yields on the device; the reference driver's outputs
         (``grid_chain_sec11.py:366-419``) come back as a :class:`ChainResult`.
 
@@ -875,7 +877,15 @@ class MarkovChain:
         (``:371-394``) computed by ``fc_run_frame_series``.  ``corrected`` adds the
         statistics the driver's quirky tallies aim at, beside them:
         ``flip_count`` / ``occupancy`` / ``last_accept`` (FC_DIAG_FLIPS_EXACT) and the
-        Rao-Blackwellised ``waits_expected``."""
+        Rao-Blackwellised ``waits_expected``.  ``sample_every`` (a positive integer) keeps the
+        plans at yields 0, every, 2 every, ... -- the states ``enumerate(chain)`` reaches at
+        ``i % every == 0`` -- in ``ChainResult.plans``, replayed on the device from the flip log
+        (DESIGN.md §5f); flip chains only."""
+        if sample_every is not None:
+            if isinstance(sample_every, bool) or not isinstance(sample_every, (int, np.integer)) or sample_every < 1:
+                raise ValueError("sample_every must be a positive integer (or None)")
+            if self.cspec.proposal == _lib.FC_PROPOSE_RECOM:
+                raise ValueError("sample_every needs a flip chain: a ReCom run keeps no flip log")
         if self.cspec.proposal == _lib.FC_PROPOSE_RECOM:
             return self._run_recom()
         diag = _lib.FC_DIAG_WAIT | _lib.FC_DIAG_HIST | _lib.FC_DIAG_EDGES | _lib.FC_DIAG_FLIPS
@@ -893,7 +903,8 @@ class MarkovChain:
         shapes = next((u for u in self.initial_state.updaters.values() if isinstance(u, Compactness)), None)
         # ... and the (first) LocalitySplits updater: locality splits over every yield (§5e)
         splits = next((u for u in self.initial_state.updaters.values() if isinstance(u, LocalitySplits)), None)
-        log = series or bool(elections) or shapes is not None or splits is not None
+        # ... and the plan samples (§5f)
+        log = series or bool(elections) or shapes is not None or splits is not None or sample_every is not None
         if log:
             diag |= _lib.FC_DIAG_SERIES
         if corrected:
@@ -926,6 +937,11 @@ class MarkovChain:
                                                              "splits_hist", "excess_hist", "parts_now", "dlocs_now")}
             res.splits.update({key: int(ss[key][0]) for key in ("sq_sum", "splits_now", "excess_now", "sq_now", "yields")})
             res.splits.update(x_max=ss["x_max"], localities=loc_labels)
+        if sample_every is not None:
+            sp_ = run.sample_plans(every=int(sample_every), c0=0, nc=1)
+            res.plans = {"yields": sp_["times"], "assignment": sp_["plans"][0], "cut": sp_["cut"][0],
+                         "nb": sp_["nb"][0], "dist0": sp_["dist0"][0], "pops": sp_["pops"][0]}
+            res._chain = self
         if elections:
             es = run.election_series(0, 1)
             res.elections = {}
@@ -1009,6 +1025,43 @@ class ChainResult:
     # splits_hist [n_loc + 1], excess_hist [min(x_max, 1023) + 1], sq_sum, splits_now, excess_now,
     # sq_now, x_max, yields
     splits: Optional[Dict[str, Any]] = None
+    # run(sample_every=...), chain 0's plans at yields 0, every, 2 every, ...: yields
+    # [m], assignment [m, n] int8 district indices (canonical node order, parts in label order), cut,
+    # nb, dist0 [m] (|cut|, |B|, Hamming distance to the initial plan), pops [m, k]
+    plans: Optional[Dict[str, np.ndarray]] = None
+    _chain: Any = field(default=None, repr=False, compare=False)  # the chain sampled() views the plans through
+
+    def sampled(self):
+        """One :class:`StateView` per sampled plan (``run(sample_every=...)``): assignment, parts,
+        ``part["cut_edges"]``, ``part["population"]``, the initial state's updaters and ``step``
+        (the yield index) as the per-step iterator's states have them, but no geometric wait and
+        no ``flips``."""
+        if self.plans is None or self._chain is None:
+            raise ValueError("no sampled plans: call MarkovChain.run(sample_every=...)")
+        pl = self.plans
+        for j in range(len(pl["yields"])):
+            yield StateView(self._chain, pl["assignment"][j].astype(np.int64), None, None, int(pl["cut"][j]),
+                            int(pl["nb"][j]), int(pl["yields"][j]))
+
+    def save_plans(self, path: str) -> str:
+        """Write the sampled plans as an ``.npz``: the arrays of ``plans`` with ``nodes`` (the
+        canonical node order of the assignment's columns) and ``labels`` (the part label of each
+        district index) beside them.  Returns the path written."""
+        if self.plans is None or self._chain is None:
+            raise ValueError("no sampled plans: call MarkovChain.run(sample_every=...)")
+        sp, lab = self._chain.cspec.spec, self._chain.cspec.labels
+        if not str(path).endswith(".npz"):
+            path = str(path) + ".npz"
+        def plain(items):  # an array that loads without pickle: the values, or their repr when ragged / mixed
+            try:
+                arr = np.asarray(list(items))
+            except ValueError:
+                arr = None
+            if arr is None or arr.dtype == object or arr.shape[0] != len(items):
+                arr = np.asarray([repr(x) for x in items])
+            return arr
+        np.savez_compressed(path, nodes=plain(list(sp.nodes)), labels=plain(list(lab)), **self.plans)
+        return path
 
     def heatmaps(self, shape=(40, 40), offset=(0, 0)) -> Dict[str, np.ndarray]:
         """The driver's ``A2`` arrays (``grid_chain_sec11.py:431-528``): ``A2[n[0], n[1]]``

@@ -834,6 +834,114 @@ int fc_run_split_series(fc_run *r, int32_t c0, int32_t nc, int64_t *cells_now, i
     return out.fetch(r, {cells_now, split_sum, parts_sum, dlocs_sum, sq_sum, splits_hist, excess_hist});
 }
 
+// ---- plan samples (fc_plans.h, fc_plans.hip) ------------------------------------
+
+int fc_run_sample_plans(fc_run *r, int32_t c0, int32_t nc, int32_t n_times, const int64_t *times, int8_t *plans,
+                        int64_t *cut, int64_t *nb, int64_t *dist0, int64_t *pops) {
+    const char *const who = "fc_run_sample_plans";
+    if (!r) return fail(FC_ERR_ARG, "fc_run_sample_plans: null run");
+    CallRules rules;
+    rules.flip_pass = "sampling plans";
+    if (int rc = check_series_call(r, who, c0, nc, rules)) return rc;
+    if (n_times < 0) return fail(FC_ERR_ARG, "fc_run_sample_plans: n_times must be at least 0");
+    if (n_times > 0 && !times) return fail(FC_ERR_ARG, "fc_run_sample_plans: null times");
+    for (int32_t j = 1; j < n_times; ++j)
+        if (times[j] <= times[j - 1]) return fail(FC_ERR_ARG, "fc_run_sample_plans: times must be strictly increasing");
+    if (nc == 0 || n_times == 0) return FC_OK;
+    SeriesCall s;
+    if (int rc = open_window(r, who, c0, nc, false, s)) return rc;
+    for (int32_t i = 0; i < nc; ++i) {
+        const fc::ChainScalars &x = s.sc[i];
+        if (times[0] < x.ser_t0)
+            return fail(FC_ERR_ARG, "fc_run_sample_plans: chain " + std::to_string(c0 + i) + ": time " +
+                                        std::to_string(times[0]) + " is before the window's first yield " +
+                                        std::to_string(x.ser_t0));
+        if (times[n_times - 1] > x.steps)
+            return fail(FC_ERR_ARG, "fc_run_sample_plans: chain " + std::to_string(c0 + i) + ": time " +
+                                        std::to_string(times[n_times - 1]) + " is after the chain's last yield " +
+                                        std::to_string(x.steps));
+    }
+    const size_t cn = (size_t)nc, nt = (size_t)n_times, npad = (size_t)r->npad;
+    const int32_t k = r->p.k, n = r->g.n;
+    int q;
+    // the staged rows are kept by the run; a larger call has to fit a tenth of the free device memory
+    // (behind them, when the rows have padding, the same rows packed to n bytes)
+    const size_t want = plans ? cn * nt * npad : 0;
+    const size_t held = want + (plans && npad != (size_t)n ? cn * nt * (size_t)n : 0);
+    if (held > r->d_pl_rows.capacity()) {
+        size_t free_b = 0, total_b = 0;
+        HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+        if (want > free_b / 10)
+            return fail(FC_ERR_ARG, "fc_run_sample_plans: " + std::to_string(want) + " bytes of staged plans (" +
+                                        std::to_string(nc) + " chains x " + std::to_string(n_times) + " times x " +
+                                        std::to_string(npad) + ") exceed a tenth of the free device memory; " +
+                                        "split the call by chains or by times");
+        if ((q = r->d_pl_rows.grow(held))) return q;
+    }
+    if (pops && !r->d_pl_pop) {
+        std::vector<int32_t> pp(npad, 0);
+        std::copy(r->g.pop.begin(), r->g.pop.begin() + n, pp.begin());
+        if ((q = r->d_pl_pop.upload(pp))) return q;
+    }
+    // times, then the chains' |cut| and |B| at the window start (open_window has left the run idle)
+    std::vector<int64_t> in(nt + 2 * cn);
+    std::copy(times, times + n_times, in.begin());
+    for (int32_t i = 0; i < nc; ++i) {
+        in[nt + i] = s.sc[i].ser_cut0;
+        in[nt + cn + i] = s.sc[i].ser_nb0;
+    }
+    if ((q = r->d_pl_in.grow(in.size()))) return q;
+    HIP_TRY(hipMemcpy(r->d_pl_in, in.data(), in.size() * 8, hipMemcpyHostToDevice));
+    OutPack out;
+    if ((q = out.reserve(r, {cn * nt, cn * nt, cn * nt, cn * nt * k}))) return q;
+    fc::PlansParams pp{};
+    pp.log = s.log;
+    pp.n_times = n_times;
+    pp.times = r->d_pl_in;
+    pp.cut0 = r->d_pl_in + nt;
+    pp.nb0 = r->d_pl_in + nt + cn;
+    pp.node_pop = r->d_pl_pop;
+    pp.plans = plans ? r->d_pl_rows.get() : nullptr;
+    pp.cut = cut ? out.at(0) : nullptr;
+    pp.nb = nb ? out.at(1) : nullptr;
+    pp.dist0 = dist0 ? out.at(2) : nullptr;
+    pp.pops = pops ? out.at(3) : nullptr;
+    for (hipEvent_t &ev : r->pl_ev)
+        if (!ev) HIP_TRY(hipEventCreate(&ev));
+    r->pl_timed = false;
+    HIP_TRY(hipEventRecord(r->pl_ev[0], r->stream));
+    const int e = fc::launch_plans(pp, r->stream);
+    if (e) return fail(FC_ERR_HIP, std::string("plan samples: ") + hipGetErrorString((hipError_t)e));
+    HIP_TRY(hipEventRecord(r->pl_ev[1], r->stream));
+    // the rows, packed to n bytes: one strided copy, pitch npad -> n, on the device, then one
+    // contiguous copy to the host (as every other reader's: no pitched copy into pageable memory)
+    if (plans) {
+        const int8_t *src = r->d_pl_rows;
+        if (npad != (size_t)n) {
+            int8_t *packed = r->d_pl_rows + want;
+            HIP_TRY(hipMemcpy2DAsync(packed, (size_t)n, src, npad, (size_t)n, cn * nt, hipMemcpyDeviceToDevice, r->stream));
+            src = packed;
+        }
+        HIP_TRY(hipMemcpyAsync(plans, src, cn * nt * (size_t)n, hipMemcpyDeviceToHost, r->stream));
+    }
+    HIP_TRY(hipEventRecord(r->pl_ev[2], r->stream));
+    if (int rc = out.fetch(r, {cut, nb, dist0, pops})) return rc;
+    r->pl_timed = true;
+    r->pl_copied = plans != nullptr;
+    return FC_OK;
+}
+
+int fc_run_sample_plans_ms(fc_run *r, float *kernel_ms, float *copy_ms) {
+    if (!r) return fail(FC_ERR_ARG, "fc_run_sample_plans_ms: null run");
+    if (!r->pl_timed) return fail(FC_ERR_ARG, "fc_run_sample_plans_ms: no fc_run_sample_plans call recorded");
+    if (kernel_ms) HIP_TRY(hipEventElapsedTime(kernel_ms, r->pl_ev[0], r->pl_ev[1]));
+    if (copy_ms) {
+        *copy_ms = 0.f;
+        if (r->pl_copied) HIP_TRY(hipEventElapsedTime(copy_ms, r->pl_ev[1], r->pl_ev[2]));
+    }
+    return FC_OK;
+}
+
 int fc_run_read_hist(fc_run *r, int64_t *cut_hist, int64_t *nb_hist) {
     if (!r || !cut_hist || !nb_hist) return fail(FC_ERR_ARG, "fc_run_read_hist: null argument");
     if (!r->d_cut_hist) return fail(FC_ERR_ARG, "fc_run_read_hist: FC_DIAG_HIST not enabled");

@@ -11,6 +11,7 @@
 #include "fc_internal.h"
 #include "fc_ladder.h"
 #include "fc_plan.h"
+#include "fc_plans.h"
 #include "fc_shapes.h"
 #include "fc_splits.h"
 #include "fc_votes.h"
@@ -174,6 +175,12 @@ struct fc_run : fc::RunShape {
     // locality-splits series (fc_run_set_localities; fc_splits.h, fc_splits.hip).  sp_n_loc 0: not set
     int32_t sp_n_loc = 0, sp_x_max = 0;
     DevBuf<int32_t> d_sp_loc;     // [n] node labels
+    // plan samples (fc_run_sample_plans; fc_plans.h, fc_plans.hip): no setter, nothing kept but buffers
+    DevBuf<int8_t> d_pl_rows;     // per call: the staged plan rows, npad bytes each, grown on demand
+    DevBuf<int64_t> d_pl_in;      // per call: times [n_times], then series_cut0 and series_nb0 [nc] each
+    DevBuf<int32_t> d_pl_pop;     // [npad] node populations, 0 beyond n (uploaded by the first call with pops)
+    hipEvent_t pl_ev[3] = {nullptr, nullptr, nullptr};  // last call: before the kernel, after it, after the row copy
+    bool pl_timed = false, pl_copied = false;           // (fc_run_sample_plans_ms)
     char kname[96] = {0};       // last launched flip-kernel instance
     // replica exchange (fc_run_set_ladders; fc_ladder.h, fc_exchange.hip).  Slots are flat: ladder
     // l's rung r is slot lad_off[l] + r
@@ -192,6 +199,8 @@ struct fc_run : fc::RunShape {
     // The caller selects the run's device first (fc_run_destroy); the buffers free themselves.
     ~fc_run() {
         for (auto &pr : launch_events) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
+        for (hipEvent_t e : pl_ev)
+            if (e) (void)hipEventDestroy(e);
         if (stream) (void)hipStreamDestroy(stream);
     }
 

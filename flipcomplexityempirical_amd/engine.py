@@ -48,6 +48,15 @@ def unpin_host(arr: np.ndarray) -> None:
     check(_lib.load().fc_host_unregister(ctypes.c_void_p(arr.ctypes.data)), "fc_host_unregister")
 
 
+def sample_times(t0: int, t_last: int, every: int, first: Optional[int] = None) -> np.ndarray:
+    """The yields ``first`` (``t0`` when None), ``+ every``, ... up to ``t_last`` inclusive, int64:
+    the times of :meth:`FlipRun.sample_plans` for a window of yields ``t0 .. t_last``."""
+    if int(every) < 1:
+        raise ValueError("every must be at least 1")
+    start = int(t0) if first is None else int(first)
+    return np.arange(start, int(t_last) + 1, int(every), dtype=np.int64)
+
+
 class FlipGraph:
     """Native graph handle (``fc_graph_create``)."""
 
@@ -663,6 +672,60 @@ class FlipRun:
         out["dlocs_now"] = occ.sum(axis=1).astype(np.int64)
         out["x_max"] = x_max
         return out
+
+    # ---- plan samples -------------------------------------------------
+    def sample_plans(self, times=None, every: Optional[int] = None, c0: int = 0, nc: Optional[int] = None,
+                     plans: bool = True, pops: bool = True) -> Dict[str, np.ndarray]:
+        """The plans chains ``c0 .. c0 + nc - 1`` hold at the yields ``times`` (absolute yield
+        indices inside the series window, strictly increasing, the same for every chain), replayed
+        on the device from the flip log (``fc_run_sample_plans``; include/flipchain.h).  ``every``
+        instead of ``times`` samples the run's own window: ``series_t0, + every, ... <= steps``.
+        Returns ``times`` ``[m]``, ``plans`` int8 ``[nc, m, n]`` (district indices as
+        :meth:`state` reports them; left out with ``plans=False``), ``cut`` / ``nb`` / ``dist0``
+        int64 ``[nc, m]`` (|cut|, |B| and the Hamming distance to the window-start plan), ``pops``
+        int64 ``[nc, m, k]`` (left out with ``pops=False``) and ``yields`` ``[nc]``, the yields of
+        each chain's window."""
+        nc = self.n_chains - c0 if nc is None else int(nc)
+        if (times is None) == (every is None):
+            raise ValueError("give either times or every")
+        st = None
+        if times is None:
+            st = self.stats()
+            sel = slice(max(int(c0), 0), max(int(c0), 0) + max(nc, 0))
+            t0, steps = st["series_t0"][sel], st["steps"][sel]
+            tm = sample_times(int(t0.max()), int(steps.min()), every) if t0.size else np.zeros(0, dtype=np.int64)
+        else:
+            tm = np.asarray(times)
+            if tm.ndim != 1:
+                raise ValueError("times must be one-dimensional")
+            if tm.size and not np.issubdtype(tm.dtype, np.integer):
+                raise ValueError("times must be integers")
+            tm = np.ascontiguousarray(tm, dtype=np.int64)
+            if tm.size > 1 and (np.diff(tm) <= 0).any():
+                raise ValueError("times must be strictly increasing")
+        m, n, k = int(tm.size), self.graph.n, self.cfg.k
+        rows = max(nc, 0)
+        out = {"times": tm, "cut": np.zeros((rows, m), dtype=np.int64), "nb": np.zeros((rows, m), dtype=np.int64),
+               "dist0": np.zeros((rows, m), dtype=np.int64)}
+        if plans:
+            out["plans"] = np.zeros((rows, m, n), dtype=np.int8)
+        if pops:
+            out["pops"] = np.zeros((rows, m, k), dtype=np.int64)
+        check(_lib.load().fc_run_sample_plans(self.handle, int(c0), nc, m, _p(tm, ctypes.c_int64),
+                                              _p(out.get("plans"), ctypes.c_int8), _p(out["cut"], ctypes.c_int64),
+                                              _p(out["nb"], ctypes.c_int64), _p(out["dist0"], ctypes.c_int64),
+                                              _p(out.get("pops"), ctypes.c_int64)), "fc_run_sample_plans")
+        st = self.stats() if st is None else st
+        out["yields"] = (st["steps"] - st["series_t0"] + 1)[c0:c0 + nc].astype(np.int64)
+        return out
+
+    def sample_plans_ms(self):
+        """Device ms of the last :meth:`sample_plans` call's kernel and of its copy of the plan rows
+        to the host (``fc_run_sample_plans_ms``; HIP events on the run's stream)."""
+        k_ms, c_ms = ctypes.c_float(0), ctypes.c_float(0)
+        check(_lib.load().fc_run_sample_plans_ms(self.handle, ctypes.byref(k_ms), ctypes.byref(c_ms)),
+              "fc_run_sample_plans_ms")
+        return float(k_ms.value), float(c_ms.value)
 
     # ---- replica exchange (DESIGN.md "Replica exchange") ------------------------------
     def set_ladders(self, ladders: Sequence[Sequence[int]], hist: bool = False) -> "FlipRun":

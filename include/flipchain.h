@@ -528,6 +528,43 @@ int fc_run_split_series(fc_run *r, int32_t c0, int32_t nc,
  * defined above.  Any output may be NULL.  Pure host function; its cost grows with the nodes. */
 int fc_splits_eval(int32_t n_loc, int32_t k, const int64_t *cells,
                    int64_t *splits, int64_t *excess, int64_t *sq);
+/* ---- plan samples: the ensemble itself, the assignments at thinned yields (the driver loop
+ * "for i, part in enumerate(chain): if i % every == 0: save(part.assignment)"), by a device replay
+ * of the flip log up to chosen yields.  Flip runs with FC_DIAG_SERIES, any k; no
+ * setter, nothing kept between calls.  Chain c has a series window of yields t = series_t0 .. steps;
+ *   a_t = the window-start assignment with every logged event of t_e <= t applied in log order (an
+ *         event's t is the first yield with a[v] = target).
+ * The call takes one list times[0 .. n_times) of absolute yield indices, strictly increasing, the
+ * same for every chain of the call, each inside every chain's window.  For sample j of chain
+ * c0 + cl:
+ *   plans[cl][j][u] = a_{times[j]}(u), the district index 0 .. k - 1 exactly as fc_run_read_state
+ *                     reports it, rows packed to n bytes;
+ *   cut[cl][j], nb[cl][j] = |cut| and |B| at that yield: the fields of the last event with
+ *                     t_e <= times[j], and series_cut0 / series_nb0 when there is none;
+ *   dist0[cl][j]    = the number of nodes u with a_{times[j]}(u) != a_{series_t0}(u), the Hamming
+ *                     distance to the window-start plan;
+ *   pops[cl][j][d]  = the sum of pop[u] over the nodes with a_{times[j]}(u) = d.
+ * All exact integers; plans is int8, the others int64.  The row of a sample at times[j] = steps is
+ * what fc_run_read_state and fc_run_read_pops return, and a sample at series_t0 is the window-start
+ * plan with dist0 = 0.  Several samples between two events repeat the same plan.
+ *
+ * Any output may be NULL to skip it (without plans no row is staged); the call synchronises; nc = 0
+ * or n_times = 0 is FC_OK and writes nothing.  FC_ERR_ARG without FC_DIAG_SERIES, for a bad chain
+ * range, n_times < 0, NULL times with n_times > 0, times not strictly increasing, a time before a
+ * chain's series_t0 or after its steps (the message names the chain and the time), a chain whose
+ * log overflowed event_cap, or when the staged rows (nc * n_times * npad bytes, npad = n rounded up
+ * to 16) exceed a tenth of the free device memory: split the call by chains or by times.
+ * FC_ERR_UNSUPPORTED for ReCom runs (no flip log).  Every n a run admits is supported: a chain's
+ * image is npad + 256 bytes of LDS, and there is no LDS refusal.  Calls interleave freely with the other series calls and with other chain ranges;
+ * checkpoint blobs are byte for byte what they were, and a restored run can be sampled at once. */
+int fc_run_sample_plans(fc_run *r, int32_t c0, int32_t nc, int32_t n_times, const int64_t *times,
+                        int8_t *plans,                               /* [nc * n_times * n] */
+                        int64_t *cut, int64_t *nb, int64_t *dist0,   /* [nc * n_times]     */
+                        int64_t *pops);                              /* [nc * n_times * k] */
+/* Device time of the last fc_run_sample_plans call that launched (HIP events on the run's stream):
+ * the kernel, and the copy of the plan rows to the host (0 when plans was NULL).  Either may be
+ * NULL.  FC_ERR_ARG before the first such call. */
+int fc_run_sample_plans_ms(fc_run *r, float *kernel_ms, float *copy_ms);
 /* Page-lock (pin) a caller's host buffer for faster device-to-host copies of the readers above
  * (hipHostRegister); unregister before freeing it. */
 int fc_host_register(void *ptr, int64_t bytes);
