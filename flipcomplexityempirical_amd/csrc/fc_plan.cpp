@@ -96,6 +96,12 @@ int check_params(const HostGraph &g, const fc_params *p, int32_t n_chains, const
             return bad(err, FC_ERR_ARG, "fc_run_create: recom needs pop_target > 0 and epsilon >= 0");
         if (g.n > 8000)
             return bad(err, FC_ERR_UNSUPPORTED, "fc_run_create: recom keeps a chain's spanning tree in LDS (n <= 8000)");
+        // fc_recom.hip sums subtree populations in int32 and marks the subset in bit 31
+        int64_t pop_total = 0;
+        for (int32_t u = 0; u < g.n; ++u) pop_total += g.pop[u];
+        if (pop_total > INT32_MAX)
+            return bad(err, FC_ERR_UNSUPPORTED, "fc_run_create: recom sums subtree populations in 31 bits (population total " +
+                                                std::to_string(pop_total) + " exceeds INT32_MAX = 2147483647)");
         if (bases)
             for (int32_t c = 1; c < n_chains; ++c)
                 if (bases[c] != bases[0]) return bad(err, FC_ERR_UNSUPPORTED, "fc_run_create: recom takes one base");

@@ -18,6 +18,8 @@
 //      population Validator and the cut_accept test, and applies the accepted state.
 // The canonical random stream (recomref.h) makes the trajectory bit-identical to the CPU
 // restatement in oracle/recomref.c.
+// Subtree populations are int32 with bit 31 as the subset mark (spop): fc_run_create refuses
+// a ReCom run on a graph whose population total exceeds INT32_MAX (fc_plan.cpp).
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -405,13 +407,16 @@ __global__ __launch_bounds__(256) void recom_kernel(RecomParams p) {
                 order[0] = (int16_t)root;
                 par[root] = -1;
                 comp[0] = 0;
-                comp[1] = 1;
             }
             wave_sync();
             int L = 0;
             {
                 int ls = 0, le = 1;
                 while (ls < le) {
+                    // level L = order[ls, le) holds a node: its end is the next level's start.  The
+                    // root has two children or more, so L + 1 <= |M| - 1 < npad always (the test
+                    // never fails; comp[npad] would be order[0]).  Written again after the level
+                    if (lane == 0 && L + 1 < npad) comp[L + 1] = (int16_t)le;
                     int nb_end = le;
                     for (int i0 = ls; i0 < le; i0 += kWave) {
                         const int i = i0 + lane;
@@ -444,7 +449,9 @@ __global__ __launch_bounds__(256) void recom_kernel(RecomParams p) {
                     ++L;
                     ls = le;
                     le = nb_end;
-                    if (lane == 0) comp[L + 1] = (int16_t)le;
+                    // (an empty level ends the walk and its end is never read: nM = comp[L]; a
+                    // path of npad nodes rooted next to an end would put it at comp[npad] = order[0])
+                    if (lane == 0 && ls < le && L + 1 < npad) comp[L + 1] = (int16_t)le;
                 }
             }
             wave_sync();

@@ -151,7 +151,9 @@ typedef struct fc_params {
     const int32_t *frozen;     /* FC_CON_FIXED: [n_frozen] endpoints of the pinned edges    */
     int32_t n_frozen;
     /* FC_PROPOSE_RECOM: recom(pop_target, epsilon, node_repeats) [gc-0.2]; the Validator is
-       the population bound, acceptance is cut_accept with `base` (1: always_accept)        */
+       the population bound, acceptance is cut_accept with `base` (1: always_accept).  The
+       graph has at most 8000 nodes and a population total of at most INT32_MAX (2^31 - 1);
+       fc_run_create answers FC_ERR_UNSUPPORTED otherwise                                    */
     double recom_pop_target;
     double recom_epsilon;
     int32_t recom_node_repeats;  /* roots tried per spanning tree (<= 0: 1)                */
