@@ -782,7 +782,7 @@ class MarkovChain:
         if cs.proposal == _lib.FC_PROPOSE_RECOM:
             cfg = RunConfig(k=len(cs.labels), labels=tuple(cs.labels), proposal=cs.proposal, seed=self.seed,
                             chain_id_offset=self.chain_id, pop_lo=cs.pop_lo, pop_hi=cs.pop_hi, base=cs.base,
-                            device=self.device, diag_mask=0, trace_chains=1 if trace else 0,
+                            device=self.device, diag_mask=diag, event_cap=event_cap, trace_chains=1 if trace else 0,
                             trace_cap=self.chunk + 16 if trace else 0, recom_pop_target=cs.recom["pop_target"],
                             recom_epsilon=cs.recom["epsilon"], recom_node_repeats=cs.recom["node_repeats"])
             return FlipRun(self._graph, cs.init[None, :], cfg)
@@ -827,16 +827,26 @@ class MarkovChain:
                 yield view
         run.close()
 
-    def _run_recom(self) -> "ChainResult":
+    def _run_recom(self, move_cap: Optional[int] = None, sample_every: Optional[int] = None) -> "ChainResult":
         """ReCom on the device: the driver's sums (|cut|, |B| over yields), acceptance
-        counts, spanning trees (``stats["bfs_levels"]``) and roots tried (``stats["bfs_calls"]``)."""
+        counts, spanning trees (``stats["bfs_levels"]``) and roots tried (``stats["bfs_calls"]``).
+        With ``move_cap`` the run keeps its move log (DESIGN.md "ReCom move log"): the per-yield
+        lists, the initial state's series updaters and the plan samples, as a flip chain's."""
         if self._graph is None:
             from .engine import FlipGraph
             self._graph = FlipGraph(self.cspec.spec)
-        run = self._make_run(trace=False, diag=0)
+        if move_cap is None:
+            run = self._make_run(trace=False, diag=0)
+        else:
+            run = self._make_run(trace=False, diag=_lib.FC_DIAG_SERIES, event_cap=move_cap)
+            readers = self._set_series_updaters(run)
         if self.total_steps > 1:
             run.steps(self.total_steps - 1)
         res = _recom_result(self, run)
+        if move_cap is not None:
+            self._read_series_updaters(run, res, readers, sample_every)
+            res.rce = run.yield_values("cut", 0)
+            res.rbn = run.yield_values("nb", 0)
         run.close()
         return res
 
@@ -865,52 +875,23 @@ class MarkovChain:
             yield view
         run.close()
 
-    # ---- fast path -------------------------------------------------------------------
-    def run(self, series: bool = True, frame: Optional[str] = "auto", corrected: bool = True,
-            sample_every: Optional[int] = None) -> "ChainResult":
-        """All ``total_steps`` yields on the device; the reference driver's outputs
-        (``grid_chain_sec11.py:366-419``) come back as a :class:`ChainResult`.
+    # ---- the series updaters of the initial state (flip and logged ReCom runs alike) ----------
+    def _series_updaters(self):
+        """(elections by key, the first Compactness, the first LocalitySplits) among the initial
+        state's updaters: what the device replays over every yield from the event log, so they
+        need the log whether or not the per-yield lists are kept."""
+        ups = self.initial_state.updaters
+        elections = {key: u for key, u in ups.items() if isinstance(u, Election)}
+        shapes = next((u for u in ups.values() if isinstance(u, Compactness)), None)
+        splits = next((u for u in ups.values() if isinstance(u, LocalitySplits)), None)
+        return elections, shapes, splits
 
-        ``series`` keeps the per-yield lists ``rce`` / ``rbn`` (``:367-369``) through the
-        device event log; ``frame`` ("sec11", "frank", None or "auto": from the
-        ``slope`` updater and the node labels) adds the ``slopes`` / ``angles`` lists
-        (``:371-394``) computed by ``fc_run_frame_series``.  ``corrected`` adds the
-        statistics the driver's quirky tallies aim at, beside them (SURVEY App. A.6):
-        ``flip_count`` / ``occupancy`` / ``last_accept`` (FC_DIAG_FLIPS_EXACT) and the
-        Rao-Blackwellised ``waits_expected``.  ``sample_every`` (a positive integer) keeps the
-        plans at yields 0, every, 2 every, ... -- the states ``enumerate(chain)`` reaches at
-        ``i % every == 0`` -- in ``ChainResult.plans``, replayed on the device from the flip log
-        (DESIGN.md §5f); flip chains only."""
-        if sample_every is not None:
-            if isinstance(sample_every, bool) or not isinstance(sample_every, (int, np.integer)) or sample_every < 1:
-                raise ValueError("sample_every must be a positive integer (or None)")
-            if self.cspec.proposal == _lib.FC_PROPOSE_RECOM:
-                raise ValueError("sample_every needs a flip chain: a ReCom run keeps no flip log")
-        if self.cspec.proposal == _lib.FC_PROPOSE_RECOM:
-            return self._run_recom()
-        diag = _lib.FC_DIAG_WAIT | _lib.FC_DIAG_HIST | _lib.FC_DIAG_EDGES | _lib.FC_DIAG_FLIPS
-        if frame == "auto":
-            frame = None
-            # (the frame-edge slope / angle of :371-394 is a two-district statistic; k = 2 only)
-            if series and len(self.cspec.labels) == 2 and \
-                    _name(self.initial_state.updaters.get("slope")) == "boundary_slope":
-                neg = any(isinstance(nd, tuple) and nd[1] < 0 for nd in self.cspec.spec.nodes)
-                frame = "frank" if neg else "sec11"
-        # Election updaters of the initial state: replayed over every yield on the device from the
-        # flip log, so they need the event log whether or not the per-yield lists are kept
-        elections = {key: u for key, u in self.initial_state.updaters.items() if isinstance(u, Election)}
-        # the (first) Compactness updater likewise: district shapes over every yield (§5d)
-        shapes = next((u for u in self.initial_state.updaters.values() if isinstance(u, Compactness)), None)
-        # ... and the (first) LocalitySplits updater: locality splits over every yield (§5e)
-        splits = next((u for u in self.initial_state.updaters.values() if isinstance(u, LocalitySplits)), None)
-        # ... and the plan samples (§5f)
-        log = series or bool(elections) or shapes is not None or splits is not None or sample_every is not None
-        if log:
-            diag |= _lib.FC_DIAG_SERIES
-        if corrected:
-            diag |= _lib.FC_DIAG_FLIPS_EXACT
-        run = self._make_run(trace=False, diag=diag, event_cap=max(self.total_steps, 1) if log else 0)
+    def _set_series_updaters(self, run, found=None):
+        """Uploads what those updaters replay against (before the first step); returns them with
+        the election column names and the locality labels, for :meth:`_read_series_updaters`."""
+        elections, shapes, splits = found if found is not None else self._series_updaters()
         col_names: List[str] = []
+        loc_labels = None
         if elections:
             for u in elections.values():
                 col_names += [c for c in u.columns if c not in col_names]
@@ -924,9 +905,11 @@ class MarkovChain:
         if splits is not None:
             loc_labels, node_loc = splits.arrays(self.initial_state.graph, self.cspec.spec)
             run.set_localities(node_loc)
-        if self.total_steps > 1:
-            run.steps(self.total_steps - 1)
-        res = ChainResult.from_run(self, run, 0)
+        return elections, shapes, splits, col_names, loc_labels
+
+    def _read_series_updaters(self, run, res: "ChainResult", readers, sample_every: Optional[int]) -> None:
+        """Fills ``res.shapes`` / ``splits`` / ``plans`` / ``elections`` from chain 0's window."""
+        elections, shapes, splits, col_names, loc_labels = readers
         if shapes is not None:
             ss = run.shape_series(0, 1)
             res.shapes = {key: ss[key][0].copy() for key in ("area_now", "perim_now", "perim_sum", "pp_now", "pp_sum")}
@@ -953,6 +936,67 @@ class MarkovChain:
                                       "wins_sum": es["wins_sum"][0, e].copy(),
                                       "gap_sum": int(es["gap_sum"][0, e]),
                                       "tally_sum": es["tally_sum"][0][:, [ja, jb]].copy()}
+
+    # ---- fast path -------------------------------------------------------------------
+    def run(self, series: bool = True, frame: Optional[str] = "auto", corrected: bool = True,
+            sample_every: Optional[int] = None, move_cap=None) -> "ChainResult":
+        """All ``total_steps`` yields on the device; the reference driver's outputs
+        (``grid_chain_sec11.py:366-419``) come back as a :class:`ChainResult`.
+
+        ``series`` keeps the per-yield lists ``rce`` / ``rbn`` (``:367-369``) through the
+        device event log; ``frame`` ("sec11", "frank", None or "auto": from the
+        ``slope`` updater and the node labels) adds the ``slopes`` / ``angles`` lists
+        (``:371-394``) computed by ``fc_run_frame_series``.  ``corrected`` adds the
+        statistics the driver's quirky tallies aim at, beside them (SURVEY App. A.6):
+        ``flip_count`` / ``occupancy`` / ``last_accept`` (FC_DIAG_FLIPS_EXACT) and the
+        Rao-Blackwellised ``waits_expected``.  ``sample_every`` (a positive integer) keeps the
+        plans at yields 0, every, 2 every, ... -- the states ``enumerate(chain)`` reaches at
+        ``i % every == 0`` -- in ``ChainResult.plans``, replayed on the device from the event log
+        (DESIGN.md §5f).
+
+        A ``partial(recom, ...)`` chain returns its final state, counters and sums.  With
+        ``move_cap`` (ReCom chains only: a positive integer, the moved nodes the log holds, or
+        ``"auto"`` = ``(total_steps - 1) * n``, which always suffices) the run logs every accepted
+        step's moved nodes (DESIGN.md "ReCom move log"), and the result also carries ``rce`` /
+        ``rbn``, ``elections`` / ``shapes`` / ``splits`` from the initial state's updaters and,
+        with ``sample_every``, ``plans``, each exactly as a flip chain fills it.  Without
+        ``move_cap`` a ReCom chain ignores those updaters and refuses ``sample_every``."""
+        recom_chain = self.cspec.proposal == _lib.FC_PROPOSE_RECOM
+        if sample_every is not None:
+            if isinstance(sample_every, bool) or not isinstance(sample_every, (int, np.integer)) or sample_every < 1:
+                raise ValueError("sample_every must be a positive integer (or None)")
+            if recom_chain and move_cap is None:
+                raise ValueError("sample_every on a ReCom chain needs its move log: pass move_cap "
+                                 "(a capacity in moved nodes, or \"auto\")")
+        if move_cap is not None:
+            if not recom_chain:
+                raise ValueError("move_cap is for ReCom chains: a flip chain sizes its event log itself")
+            if move_cap == "auto" and isinstance(move_cap, str):
+                move_cap = max((self.total_steps - 1) * self.cspec.spec.n, 1)
+            elif isinstance(move_cap, bool) or not isinstance(move_cap, (int, np.integer)) or move_cap < 1:
+                raise ValueError("move_cap must be a positive integer, \"auto\" or None")
+        if recom_chain:
+            return self._run_recom(None if move_cap is None else int(move_cap), sample_every)
+        diag = _lib.FC_DIAG_WAIT | _lib.FC_DIAG_HIST | _lib.FC_DIAG_EDGES | _lib.FC_DIAG_FLIPS
+        if frame == "auto":
+            frame = None
+            # (the frame-edge slope / angle of :371-394 is a two-district statistic; k = 2 only)
+            if series and len(self.cspec.labels) == 2 and \
+                    _name(self.initial_state.updaters.get("slope")) == "boundary_slope":
+                neg = any(isinstance(nd, tuple) and nd[1] < 0 for nd in self.cspec.spec.nodes)
+                frame = "frank" if neg else "sec11"
+        readers = self._series_updaters()
+        log = series or bool(readers[0]) or readers[1] is not None or readers[2] is not None or sample_every is not None
+        if log:
+            diag |= _lib.FC_DIAG_SERIES
+        if corrected:
+            diag |= _lib.FC_DIAG_FLIPS_EXACT
+        run = self._make_run(trace=False, diag=diag, event_cap=max(self.total_steps, 1) if log else 0)
+        readers = self._set_series_updaters(run, readers)
+        if self.total_steps > 1:
+            run.steps(self.total_steps - 1)
+        res = ChainResult.from_run(self, run, 0)
+        self._read_series_updaters(run, res, readers, sample_every)
         if corrected:
             sp = self.cspec.spec
             xf, xo, xl = run.flips_exact()

@@ -491,7 +491,7 @@ int fc_run_steps(fc_run *r, int64_t n_steps, int64_t max_draws, void *hip_stream
     HIP_TRY(hipEventRecord(evp.first, s));
     if (r->p.proposal == FC_PROPOSE_RECOM) {
         const fc::RecomParams q = recom_params(r, n_steps, max_draws, k.prof);
-        const int e = fc::launch_recom(q, r->g.ring_max, s, r->kname, sizeof r->kname);
+        const int e = fc::launch_recom(q, r->d_events, r->ev_cap, r->g.ring_max, s, r->kname, sizeof r->kname);
         if (e != 0) return fail(FC_ERR_HIP, std::string("recom kernel launch: ") + hipGetErrorString((hipError_t)e));
         return finish_launches(r, evp, s);
     }

@@ -214,7 +214,11 @@ struct RecomParams {
 // fc_recom.hip's layout: 8 B (keys / tree CSR + parents / subtree populations) + component +
 // order (2 + 2 B) + tree-edge bits (1 B for RMAX = 8, else 2) + assignment (1 B) per node
 inline int recom_lds_bytes(int n, int ring_max) { return (ring_max == 8 ? 14 : 15) * ((n + 15) & ~15); }
-int launch_recom(const RecomParams &p, int ring_max, void *stream, char *name, size_t name_cap);
+// events [n_chains * ev_cap], ev_cap > 0: the run keeps a move log (FC_DIAG_SERIES) and the logging
+// instance recom_log_kernel runs; it takes both as arguments of its own after RecomParams, so the
+// lean instance's argument layout is what it was.  Null / 0: the lean instance recom_kernel
+int launch_recom(const RecomParams &p, fc_event *events, int64_t ev_cap, int ring_max, void *stream, char *name,
+                 size_t name_cap);
 
 // Launch wrappers.  Return a hipError_t as int.
 // `name` (may be null) receives the launched instance, spelled as rocprofv3 reports it.

@@ -20,18 +20,27 @@ int check_event_overflow(const fc_run *r, const char *who, int32_t chain, const 
 
 // ---- the driver the series calls share (DESIGN.md §4 "Series window") -------------------------
 
+// what a ReCom run without a move log is told (it has no event buffer: fc_run_create makes one
+// for FC_DIAG_SERIES with an event_cap, and the logging kernel instance fills it)
+int no_move_log(const std::string &who, const char *pass) {
+    return fail(FC_ERR_UNSUPPORTED, who + ": " + pass + " replays the event log, and this ReCom run keeps none; create "
+                                        "the run with FC_DIAG_SERIES and an event_cap to log its moves");
+}
+
 struct CallRules {
-    const char *flip_pass = nullptr;  // the pass replays flips, which a ReCom run does not log: its name
+    const char *log_pass = nullptr;   // the pass's name, for a ReCom run without a move log (no_move_log)
     const char *unset = nullptr;      // the setter the pass needs and the run has not had, or null
     const char *k2_only = nullptr;    // the pass follows k = 2 flips: what to say of another run
+    const char *flips_only = nullptr; // the pass has an output per flip: what to say of a ReCom run
 };
 
 // The checks every series call `who` over chains [c0, c0 + nc) makes of the run and the range,
 // before any device work.
 int check_series_call(const fc_run *r, const char *who, int32_t c0, int32_t nc, const CallRules &rules) {
     const std::string w(who);
-    if (rules.flip_pass && r->p.proposal == FC_PROPOSE_RECOM)
-        return fail(FC_ERR_UNSUPPORTED, w + ": " + rules.flip_pass + " replays the flip log (not ReCom)");
+    const bool recom = r->p.proposal == FC_PROPOSE_RECOM;
+    if (rules.flips_only && recom) return fail(FC_ERR_UNSUPPORTED, w + ": " + rules.flips_only);
+    if (rules.log_pass && recom && !r->d_events) return no_move_log(w, rules.log_pass);
     if (!r->d_events) return fail(FC_ERR_ARG, w + ": FC_DIAG_SERIES not enabled");
     if (rules.unset) return fail(FC_ERR_ARG, w + ": call " + rules.unset + " first");
     if (rules.k2_only && r->p.k != 2) return fail(FC_ERR_UNSUPPORTED, w + ": " + rules.k2_only);
@@ -397,6 +406,8 @@ int fc_run_frame_series(fc_run *r, int32_t c0, int32_t nc, int32_t n_frame, cons
     CallRules rules;
     rules.k2_only = "the frame series follows k = 2 flips (the reference computes boundary_slope only in its "
                     "two-district drivers)";
+    rules.flips_only = "a ReCom step moves many nodes at once (a burst of events with one t), and the "
+                       "frame series has an entry per event: it follows flip runs only";
     if (int rc = check_series_call(r, "fc_run_frame_series", c0, nc, rules)) return rc;
     if (n_frame < 0 || n_frame > 256) return fail(FC_ERR_UNSUPPORTED, "fc_run_frame_series: at most 256 frame edges");
     const int32_t n = r->g.n;
@@ -440,6 +451,8 @@ int fc_run_frame_series_changes(fc_run *r, int32_t c0, int32_t nc, int32_t n_fra
     if (!query && (!t || !slope || !angle)) return fail(FC_ERR_ARG, "fc_run_frame_series_changes: null output");
     CallRules rules;
     rules.k2_only = "k = 2 runs only";
+    rules.flips_only = "a ReCom step moves many nodes at once (a burst of events with one t), and the "
+                       "frame series has an entry per event: it follows flip runs only";
     if (int rc = check_series_call(r, "fc_run_frame_series_changes", c0, nc, rules)) return rc;
     if (n_frame < 0 || n_frame > 256)
         return fail(FC_ERR_UNSUPPORTED, "fc_run_frame_series_changes: at most 256 frame edges");
@@ -553,8 +566,7 @@ int fc_election_eval(int32_t k, const int64_t *a, const int64_t *b, int32_t *sea
 int fc_run_set_elections(fc_run *r, int32_t n_cols, const int32_t *node_cols, int32_t n_elections,
                          const int32_t *col_a, const int32_t *col_b, int32_t n_gap_edges, const int64_t *gap_edges) {
     if (!r || !node_cols) return fail(FC_ERR_ARG, "fc_run_set_elections: null argument");
-    if (r->p.proposal == FC_PROPOSE_RECOM)
-        return fail(FC_ERR_UNSUPPORTED, "fc_run_set_elections: the election series replays the flip log (not ReCom)");
+    if (r->p.proposal == FC_PROPOSE_RECOM && !r->d_events) return no_move_log("fc_run_set_elections", "the election series");
     if (!r->d_events) return fail(FC_ERR_ARG, "fc_run_set_elections: FC_DIAG_SERIES not enabled");
     if (n_cols < 1 || n_cols > fc::kVoteMaxCols) return fail(FC_ERR_ARG, "fc_run_set_elections: n_cols must be 1..8");
     if (n_elections < 0 || n_elections > fc::kVoteMaxElections)
@@ -652,8 +664,7 @@ int fc_shape_score(int64_t area, int64_t perim, int64_t *q) {
 int fc_run_set_shapes(fc_run *r, const int32_t *node_area, const int32_t *node_ext, const int32_t *edge_len,
                       int32_t n_pp_edges, const int64_t *pp_edges) {
     if (!r || !node_area) return fail(FC_ERR_ARG, "fc_run_set_shapes: null argument");
-    if (r->p.proposal == FC_PROPOSE_RECOM)
-        return fail(FC_ERR_UNSUPPORTED, "fc_run_set_shapes: the compactness series replays the flip log (not ReCom)");
+    if (r->p.proposal == FC_PROPOSE_RECOM && !r->d_events) return no_move_log("fc_run_set_shapes", "the compactness series");
     if (!r->d_events) return fail(FC_ERR_ARG, "fc_run_set_shapes: FC_DIAG_SERIES not enabled");
     const int32_t n = r->g.n, E = r->g.n_edges;
     if (E > 0 && !edge_len) return fail(FC_ERR_ARG, "fc_run_set_shapes: null edge_len");
@@ -771,9 +782,8 @@ int fc_splits_eval(int32_t n_loc, int32_t k, const int64_t *cells, int64_t *spli
 
 int fc_run_set_localities(fc_run *r, int32_t n_loc, const int32_t *node_loc) {
     if (!r || !node_loc) return fail(FC_ERR_ARG, "fc_run_set_localities: null argument");
-    if (r->p.proposal == FC_PROPOSE_RECOM)
-        return fail(FC_ERR_UNSUPPORTED,
-                    "fc_run_set_localities: the locality-splits series replays the flip log (not ReCom)");
+    if (r->p.proposal == FC_PROPOSE_RECOM && !r->d_events)
+        return no_move_log("fc_run_set_localities", "the locality-splits series");
     if (!r->d_events) return fail(FC_ERR_ARG, "fc_run_set_localities: FC_DIAG_SERIES not enabled");
     const int32_t n = r->g.n, k = r->p.k;
     if (n_loc < 1 || n_loc > n) return fail(FC_ERR_ARG, "fc_run_set_localities: n_loc must be 1..n");
@@ -841,7 +851,7 @@ int fc_run_sample_plans(fc_run *r, int32_t c0, int32_t nc, int32_t n_times, cons
     const char *const who = "fc_run_sample_plans";
     if (!r) return fail(FC_ERR_ARG, "fc_run_sample_plans: null run");
     CallRules rules;
-    rules.flip_pass = "sampling plans";
+    rules.log_pass = "sampling plans";
     if (int rc = check_series_call(r, who, c0, nc, rules)) return rc;
     if (n_times < 0) return fail(FC_ERR_ARG, "fc_run_sample_plans: n_times must be at least 0");
     if (n_times > 0 && !times) return fail(FC_ERR_ARG, "fc_run_sample_plans: null times");

@@ -378,7 +378,9 @@ class FlipRun:
 
     # ---- series diagnostics (FC_DIAG_SERIES) ------------------------------------------
     def events(self, chain: int = 0) -> np.ndarray:
-        """Accepted flips of ``chain`` in the current series window (``fc_event``)."""
+        """Events of ``chain`` in the current series window (``fc_event``): the accepted flips of a
+        flip run; of a ReCom run with a move log, one event per node an accepted step moved, the
+        events of one step sharing their ``t``, ``cut`` and ``nb`` (a burst, ascending node id)."""
         cap = int(self.cfg.event_cap)
         out = np.zeros(cap, dtype=EVENT_DTYPE)
         n = ctypes.c_int64(0)
@@ -585,7 +587,7 @@ class FlipRun:
 
     def election_series(self, c0: int = 0, nc: Optional[int] = None) -> Dict[str, np.ndarray]:
         """Election statistics of chains ``c0 .. c0 + nc - 1`` over the series window, replayed
-        on the device from the flip log (``fc_run_election_series``; include/flipchain.h):
+        on the device from the event log (``fc_run_election_series``; include/flipchain.h):
         ``tally_now`` / ``tally_sum`` ``[nc, k, n_cols]``, ``seats_hist`` ``[nc, n_el, k + 1]``,
         ``wins_sum`` ``[nc, n_el, k]``, ``gap_sum`` ``[nc, n_el]``, ``gap_hist``
         ``[nc, n_el, n_edges + 1]`` (only with ``gap_edges``) and ``yields`` ``[nc]``, the yields of
@@ -623,7 +625,7 @@ class FlipRun:
 
     def shape_series(self, c0: int = 0, nc: Optional[int] = None) -> Dict[str, np.ndarray]:
         """District shapes of chains ``c0 .. c0 + nc - 1`` over the series window, replayed on the
-        device from the flip log (``fc_run_shape_series``; include/flipchain.h): ``area_now`` /
+        device from the event log (``fc_run_shape_series``; include/flipchain.h): ``area_now`` /
         ``perim_now`` / ``perim_sum`` / ``pp_now`` / ``pp_sum`` ``[nc, k]``, ``pp_min_sum`` ``[nc]``,
         ``pp_hist`` ``[nc, k, n_edges + 1]`` and ``pp_min_hist`` ``[nc, n_edges + 1]`` (only with
         ``pp_edges``) and ``yields`` ``[nc]``, the yields of each chain's window.  All int64; the
@@ -653,7 +655,7 @@ class FlipRun:
 
     def split_series(self, c0: int = 0, nc: Optional[int] = None) -> Dict[str, np.ndarray]:
         """Locality splits of chains ``c0 .. c0 + nc - 1`` over the series window, replayed on the
-        device from the flip log (``fc_run_split_series``; include/flipchain.h): ``cells_now``
+        device from the event log (``fc_run_split_series``; include/flipchain.h): ``cells_now``
         ``[nc, n_loc, k]``, ``split_sum`` / ``parts_sum`` ``[nc, n_loc]``, ``dlocs_sum`` ``[nc, k]``,
         ``sq_sum`` ``[nc]``, ``splits_hist`` ``[nc, n_loc + 1]``, ``excess_hist`` ``[nc, X + 1]``
         (``X = min(x_max, 1023)``) and ``yields`` ``[nc]``, all int64; and, derived from ``cells_now``
@@ -678,7 +680,7 @@ class FlipRun:
                      plans: bool = True, pops: bool = True) -> Dict[str, np.ndarray]:
         """The plans chains ``c0 .. c0 + nc - 1`` hold at the yields ``times`` (absolute yield
         indices inside the series window, strictly increasing, the same for every chain), replayed
-        on the device from the flip log (``fc_run_sample_plans``; include/flipchain.h).  ``every``
+        on the device from the event log (``fc_run_sample_plans``; include/flipchain.h).  ``every``
         instead of ``times`` samples the run's own window: ``series_t0, + every, ... <= steps``.
         Returns ``times`` ``[m]``, ``plans`` int8 ``[nc, m, n]`` (district indices as
         :meth:`state` reports them; left out with ``plans=False``), ``cut`` / ``nb`` / ``dist0``

@@ -141,7 +141,10 @@ typedef struct fc_params {
     int32_t wmax;              /* PAIR: district slots per node draw (<= 0: min(max deg, k-1)) */
     int32_t hit_lo, hit_hi;    /* hitting time: first yield with hit_lo <= |cut| <= hit_hi
                                   (hit_lo > hit_hi: off)                                     */
-    int64_t event_cap;         /* FC_DIAG_SERIES: events kept per chain per series window    */
+    int64_t event_cap;         /* FC_DIAG_SERIES: events kept per chain per series window: one
+                                  per accepted flip; a ReCom run logs one per node an accepted
+                                  step moves (its move log), so (steps in the window) * n always
+                                  suffices (the measured mean: DESIGN.md "ReCom move log")   */
     /* accept / constraint variants (k = 2; all zero = Validator([single_flip_contiguous,
        popbound]) + cut_accept, the reference's configuration)                               */
     int32_t accept;            /* FC_ACCEPT_*                                                */
@@ -240,14 +243,18 @@ typedef struct fc_chain_stats {
     int32_t last_flip;    /* node flipped to create the current state (-1: initial)       */
     int32_t stuck;        /* a launch hit max_draws before finishing its steps            */
     int64_t hit_time;     /* first yield index with |cut| in [hit_lo, hit_hi], -1: not yet  */
-    int64_t events;       /* accepted flips in the current series window (may exceed cap) */
+    int64_t events;       /* events in the current series window (may exceed cap): accepted flips;
+                             for a ReCom run with a move log, the nodes its accepted steps moved */
     int64_t series_t0;    /* yield index at which the series window starts                */
     int32_t series_cut0;  /* |cut| of that yield                                           */
     int32_t series_nb0;   /* |B| of that yield                                             */
 } fc_chain_stats;
 
 /* One accepted flip (FC_DIAG_SERIES): yield t is the first state with a[v] = target;
- * |cut| and |B| hold from yield t until the next event's t (16 B). */
+ * |cut| and |B| hold from yield t until the next event's t (16 B).
+ * A ReCom run with a move log writes one event per node an accepted step moves: a burst of events
+ * in ascending v that share t, cut and nb (those of the step's new state).  An accepted step that
+ * reproduces the plan, like a rejected one, writes nothing. */
 typedef struct fc_event {
     int64_t t;
     uint16_t v;
@@ -348,6 +355,16 @@ int fc_run_read_flips_exact(fc_run *r, int64_t *flip_count, int64_t *occupancy, 
  * (geom_wait :147-148), from the |B| histogram.  Needs FC_DIAG_HIST (FC_ERR_ARG otherwise). */
 int fc_run_read_wait_expected(fc_run *r, double *out);
 /* ---- series diagnostics (FC_DIAG_SERIES): the per-yield lists rce / rbn (:367-369) ----- */
+/* The event log and every pass below serve flip runs and ReCom runs alike.  A ReCom run created
+ * with FC_DIAG_SERIES and an event_cap keeps a move log (the kernel instance fc::recom_log_kernel);
+ * one created without answers FC_ERR_UNSUPPORTED to the setters and series calls of the election,
+ * compactness, locality-splits and plan-sample sections (create it with FC_DIAG_SERIES and an
+ * event_cap), and FC_ERR_ARG to fc_run_read_events and fc_run_autocorr, like any run without a log.
+ * The burst convention: several events may share one t (the nodes one ReCom step moves), and
+ *   a_t = the window-start assignment with every event of t_e <= t applied,
+ * so the assignments between the events of one burst are not plans: they hold for no yield, weigh
+ * nothing in any sum or histogram, and are never sampled.  |cut| and |B| at yield t are those of
+ * the last event with t_e <= t.  A flip run's events have strictly increasing t. */
 /* Events of one chain's current window (*len = events recorded, may exceed cap). */
 int fc_run_read_events(fc_run *r, int32_t chain, fc_event *out, int64_t cap, int64_t *len);
 /* Start a new window at the current yield (events dropped; hit_time is kept). */
@@ -360,7 +377,8 @@ int fc_run_series_reset(fc_run *r);
 int fc_run_autocorr(fc_run *r, const int32_t *lags, int32_t nlags, int64_t *lag_sums, double *acf);
 /* Frame-edge slope / angle series of chains [c0, c0 + nc) over the current window
  * (boundary_slope + the driver's loop body, grid_chain_sec11.py:55-78,371-394;
- * Frankenstein_chain.py:55-78,399-422).  k = 2 only (FC_ERR_UNSUPPORTED otherwise).
+ * Frankenstein_chain.py:55-78,399-422).  k = 2 flip runs only (FC_ERR_UNSUPPORTED otherwise: the
+ * outputs have an entry per event, which means nothing inside a ReCom burst).
  *   frame_u/v [n_frame <= 256]: the frame edges boundary_slope can return, in the order
  *                               whose first two cut members are used;
  *   mid_xy [2 n_frame]:          their midpoints (enda / endb) in the reference's node
@@ -384,13 +402,14 @@ int fc_run_frame_series(fc_run *r, int32_t c0, int32_t nc, int32_t n_frame, cons
  * otherwise cap (entries per output array) must be >= offsets[nc] (FC_ERR_ARG, offsets still
  * filled, so a caller with buffers of a guessed size calls once and only re-calls on a miss).
  * The run keeps the device tables and outputs between calls (one call per launch of a driver
- * loop costs two kernel passes, one small round trip for the offsets and three copies).  k = 2. */
+ * loop costs two kernel passes, one small round trip for the offsets and three copies).  k = 2
+ * flip runs only (FC_ERR_UNSUPPORTED otherwise, ReCom runs with a move log included). */
 int fc_run_frame_series_changes(fc_run *r, int32_t c0, int32_t nc, int32_t n_frame, const int32_t *frame_u,
                                 const int32_t *frame_v, const double *mid_xy, double cx, double cy, int64_t cap,
                                 int64_t *offsets, int64_t *t, double *slope, double *angle);
 /* ---- election series: what the sampled plans do (gerrychain's Tally / Election updaters and the
- * seats / efficiency-gap outlier histograms), by a device replay of the flip log against node
- * columns.  Flip runs with FC_DIAG_SERIES, any k.
+ * seats / efficiency-gap outlier histograms), by a device replay of the event log against node
+ * columns.  Flip runs, and ReCom runs with a move log (above), with FC_DIAG_SERIES; any k.
  * Over the window's yields t = series_t0 .. steps, with a_t the assignment at yield t:
  *   S_t[d][j]       = sum of node_cols[u][j] over the nodes u with a_t(u) = d;
  *   tally_now[d][j] = S at the current yield;      tally_sum[d][j] = sum_t S_t[d][j];
@@ -413,7 +432,7 @@ int fc_run_frame_series_changes(fc_run *r, int32_t c0, int32_t nc, int32_t n_fra
  * fc_run_election_series fills the outputs of chains [c0, c0 + nc) (any may be NULL to skip it)
  * and synchronises.  FC_ERR_ARG without FC_DIAG_SERIES, before fc_run_set_elections, for a bad
  * chain range, for gap_hist without edges, for a window of 2^30 yields or more, or when a chain's
- * log overflowed event_cap; FC_ERR_UNSUPPORTED for ReCom runs (no flip log). */
+ * log overflowed event_cap; FC_ERR_UNSUPPORTED for ReCom runs without a move log. */
 int fc_run_set_elections(fc_run *r, int32_t n_cols, const int32_t *node_cols, int32_t n_elections,
                          const int32_t *col_a, const int32_t *col_b, int32_t n_gap_edges, const int64_t *gap_edges);
 int fc_run_election_series(fc_run *r, int32_t c0, int32_t nc,
@@ -428,8 +447,8 @@ int fc_run_election_series(fc_run *r, int32_t c0, int32_t nc,
 int fc_election_eval(int32_t k, const int64_t *a, const int64_t *b, int32_t *seats, int64_t *gap);
 /* ---- compactness series: how the sampled plans are shaped (gerrychain's perimeter,
  * exterior_boundaries, interior_boundaries and polsby_popper updaters), by a device replay of the
- * flip log against node areas and boundary lengths.  Flip runs with
- * FC_DIAG_SERIES, any k.  Inputs, per run, not trajectory state:
+ * event log against node areas and boundary lengths.  Flip runs, and ReCom runs with
+ * a move log (above), with FC_DIAG_SERIES; any k.  Inputs, per run, not trajectory state:
  *   node_area[n]  int32 >= 0, total <= 2^31 - 1;
  *   node_ext[n]   int32 >= 0: the length of the unit's boundary on the outside of the whole region
  *                 (gerrychain's node attribute boundary_perim); NULL: all 0;
@@ -459,12 +478,12 @@ int fc_election_eval(int32_t k, const int64_t *a, const int64_t *b, int32_t *sea
  * again to replace them.  Checkpoint blobs do not hold them (and are byte for byte what they
  * were), so a restored run needs fc_run_set_shapes again.  FC_ERR_ARG without FC_DIAG_SERIES, for
  * negative values or totals over 2^31 - 1, for edges that do not ascend or more than 64 of them;
- * FC_ERR_UNSUPPORTED for ReCom runs (no flip log) and when a chain's image (assignment,
+ * FC_ERR_UNSUPPORTED for ReCom runs without a move log and when a chain's image (assignment,
  * histograms, a chunk's neighbour rows) does not fit 48 KB of LDS.
  * fc_run_shape_series fills the outputs of chains [c0, c0 + nc) (any may be NULL to skip it) and
  * synchronises.  FC_ERR_ARG without FC_DIAG_SERIES, before fc_run_set_shapes, for a bad chain
  * range, for a histogram without edges, for a window of 2^30 yields or more, or when a chain's log
- * overflowed event_cap; FC_ERR_UNSUPPORTED for ReCom runs. */
+ * overflowed event_cap; FC_ERR_UNSUPPORTED for ReCom runs without a move log. */
 int fc_run_set_shapes(fc_run *r, const int32_t *node_area, const int32_t *node_ext, const int32_t *edge_len,
                       int32_t n_pp_edges, const int64_t *pp_edges);
 int fc_run_shape_series(fc_run *r, int32_t c0, int32_t nc,
@@ -478,8 +497,8 @@ int fc_run_shape_series(fc_run *r, int32_t c0, int32_t nc,
 int fc_shape_score(int64_t area, int64_t perim, int64_t *q);
 /* ---- locality-splits series: how the sampled plans cut through administrative units
  * (gerrychain's county_splits updater and the split / pieces counts reported beside an ensemble),
- * by a device replay of the flip log against a node labelling.  Flip runs with
- * FC_DIAG_SERIES, any k.  Input, per run, not trajectory state:
+ * by a device replay of the event log against a node labelling.  Flip runs, and ReCom
+ * runs with a move log (above), with FC_DIAG_SERIES; any k.  Input, per run, not trajectory state:
  *   node_loc[n]  int32 labels in [0, n_loc), 1 <= n_loc <= n, every label used by at least one
  *                node.  One labelling per run; fc_run_set_localities is callable again to replace
  *                it (municipalities after counties: a second set + read over the same window).
@@ -508,13 +527,13 @@ int fc_shape_score(int64_t area, int64_t perim, int64_t *q);
  * fc_run_set_localities validates and uploads the labels.  Checkpoint blobs do not hold them (and
  * are byte for byte what they were), so a restored run needs fc_run_set_localities again.
  * FC_ERR_ARG without FC_DIAG_SERIES, for n_loc < 1 or > n, a label out of range or an unused label;
- * FC_ERR_UNSUPPORTED for ReCom runs (no flip log) and when a chain's image does not fit 48 KB of
+ * FC_ERR_UNSUPPORTED for ReCom runs without a move log and when a chain's image does not fit 48 KB of
  * LDS: 8 (3 n_loc + X + 34) + 4 n_loc + 4 ceil(n_loc k / 2) + the assignment row (n padded to 16)
  * bytes; n <= 16,384 with n_loc <= 256 and n_loc k <= 4,096 always fits.
  * fc_run_split_series fills the outputs of chains [c0, c0 + nc) (any may be NULL to skip it) and
  * synchronises.  FC_ERR_ARG without FC_DIAG_SERIES, before fc_run_set_localities, for a bad chain
  * range, for a window of 2^30 yields or more, or when a chain's log overflowed event_cap;
- * FC_ERR_UNSUPPORTED for ReCom runs.  Calls interleave freely with the election, compactness and
+ * FC_ERR_UNSUPPORTED for ReCom runs without a move log.  Calls interleave freely with the election, compactness and
  * frame series and with other chain ranges. */
 int fc_run_set_localities(fc_run *r, int32_t n_loc, const int32_t *node_loc);
 int fc_run_split_series(fc_run *r, int32_t c0, int32_t nc,
@@ -532,7 +551,8 @@ int fc_splits_eval(int32_t n_loc, int32_t k, const int64_t *cells,
                    int64_t *splits, int64_t *excess, int64_t *sq);
 /* ---- plan samples: the ensemble itself, the assignments at thinned yields (the driver loop
  * "for i, part in enumerate(chain): if i % every == 0: save(part.assignment)"), by a device replay
- * of the flip log up to chosen yields.  Flip runs with FC_DIAG_SERIES, any k; no
+ * of the event log up to chosen yields.  Flip runs, and ReCom runs with a move log
+ * (above), with FC_DIAG_SERIES; any k; no
  * setter, nothing kept between calls.  Chain c has a series window of yields t = series_t0 .. steps;
  *   a_t = the window-start assignment with every logged event of t_e <= t applied in log order (an
  *         event's t is the first yield with a[v] = target).
@@ -556,7 +576,7 @@ int fc_splits_eval(int32_t n_loc, int32_t k, const int64_t *cells,
  * chain's series_t0 or after its steps (the message names the chain and the time), a chain whose
  * log overflowed event_cap, or when the staged rows (nc * n_times * npad bytes, npad = n rounded up
  * to 16) exceed a tenth of the free device memory: split the call by chains or by times.
- * FC_ERR_UNSUPPORTED for ReCom runs (no flip log).  Every n a run admits is supported: a chain's
+ * FC_ERR_UNSUPPORTED for ReCom runs without a move log.  Every n a run admits is supported: a chain's
  * image is npad + 256 bytes of LDS, and there is no LDS refusal.  Calls interleave freely with the other series calls and with other chain ranges;
  * checkpoint blobs are byte for byte what they were, and a restored run can be sampled at once. */
 int fc_run_sample_plans(fc_run *r, int32_t c0, int32_t nc, int32_t n_times, const int64_t *times,
