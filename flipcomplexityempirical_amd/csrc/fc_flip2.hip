@@ -1109,7 +1109,7 @@ __global__ __launch_bounds__(256, (RMAX == 8 ? 4 : 1)) void flip2_kernel(KParams
             } else {
                 g = philox4x32_10((uint32_t)d, (uint32_t)(d >> 32), chain_gid, 1u, p.seed_lo, p.seed_hi);
             }
-            my_wait = geom_from(u53(g.x0, g.x1), p.log1mp[nb_after]);
+            my_wait = geom_wait_of(g.x0, g.x1, p.log1mp[nb_after]);
         }
         // With the queue on, every accepted state's terms of the sums are formed by wait_flush
         // from its queue entry (|cut|, |B|, run length), and the start state's run joins the

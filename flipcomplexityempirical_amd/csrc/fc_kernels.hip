@@ -219,7 +219,7 @@ __global__ __launch_bounds__(256, (RMAX == 8 ? FC_K_WAVES8 : 1)) void flip_kerne
         if (lane < qn) {
             const uint64_t dq = q_d[lane];
             const Words4 g = philox4x32_10((uint32_t)dq, (uint32_t)(dq >> 32), chain_gid, 1u, p.seed_lo, p.seed_hi);
-            w = geom_from(u53(g.x0, g.x1), p.log1mp[q_nb[lane]]);
+            w = geom_wait_of(g.x0, g.x1, p.log1mp[q_nb[lane]]);
             acc_wait += w * (int64_t)q_run[lane];
         }
         wait_cur = (int64_t)__shfl((long long)w, qn - 1);
@@ -1166,8 +1166,7 @@ __global__ __launch_bounds__(256, (RMAX == 8 ? FC_K_WAVES8 : 1)) void flip_kerne
             } else {
                 g = philox4x32_10((uint32_t)d, (uint32_t)(d >> 32), chain_gid, 1u, p.seed_lo, p.seed_hi);
             }
-            const double U = u53(g.x0, g.x1);
-            my_wait = geom_from(U, p.log1mp[nb_after]);
+            my_wait = geom_wait_of(g.x0, g.x1, p.log1mp[nb_after]);
         }
         if (is_acc) {
             acc_cut += (int64_t)cut_after * run_len;
