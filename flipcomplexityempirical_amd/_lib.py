@@ -31,6 +31,7 @@ FC_FLAG_SERIES_TWO_PASS = 0x2  # fc_run_frame_series_changes' two-pass form (cro
 FC_FLAG_TALLY_LOG_SMALL = 0x4  # a 64-entry tally log: the overflow path's atomics (cross-check)
 FC_FLAG_NB_PAIRS = 0x8  # k > 2: |b_nodes| counts the pair updater's (node, district) pairs (:151-153)
 FC_FLAG_VOTES_GLOBAL_CUR = 0x10  # fc_run_election_series: current assignment in a global row (cross-check)
+FC_HEAT_LDS_ROWS = 0x1  # fc_run_heat_series: the requested arrays privatised in LDS when they fit (cross-check)
 FC_ACCEPT_CUT, FC_ACCEPT_UNIFORM, FC_ACCEPT_ANNEAL = 0, 1, 2
 FC_LADDER_HIST = 0x1  # fc_run_set_ladders: per-rung |cut| / |B| histograms
 FC_CON_CONTIG, FC_CON_POP, FC_CON_BOUNDARY, FC_CON_FIXED, FC_CON_EMPTY = 0x1, 0x2, 0x4, 0x8, 0x100
@@ -50,6 +51,7 @@ EXPORTED = [
     "fc_run_set_shapes", "fc_run_shape_series", "fc_shape_score",
     "fc_run_set_localities", "fc_run_split_series", "fc_splits_eval",
     "fc_run_sample_plans", "fc_run_sample_plans_ms",
+    "fc_run_heat_series", "fc_run_heat_series_info", "fc_graph_heat_rows",
     "fc_run_destroy",
     "fc_device_count", "fc_device_pci_id", "fc_last_error", "fc_build_flags", "fc_build_id",
 ]
@@ -251,6 +253,9 @@ def load(build_if_missing: bool = True, allow_variant: bool = False):
     L.fc_splits_eval.argtypes = [i32, i32, _P(i64), _P(i64), _P(i64), _P(i64)]
     L.fc_run_sample_plans.argtypes = [vp, i32, i32, i32, _P(i64), _P(ctypes.c_int8)] + [_P(i64)] * 4
     L.fc_run_sample_plans_ms.argtypes = [vp, _P(ctypes.c_float), _P(ctypes.c_float)]
+    L.fc_run_heat_series.argtypes = [vp, i32, i32, u32] + [_P(i64)] * 6
+    L.fc_run_heat_series_info.argtypes = [vp, _P(i32), _P(i64), _P(ctypes.c_float)]
+    L.fc_graph_heat_rows.argtypes = [vp, _P(i32), _P(i32), _P(i32)]
     L.fc_device_pci_id.argtypes = [i32, ctypes.c_char_p, i32]
     L.fc_run_destroy.argtypes = [vp]
     L.fc_run_destroy.restype = None

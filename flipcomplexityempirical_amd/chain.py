@@ -847,6 +847,7 @@ class MarkovChain:
             self._read_series_updaters(run, res, readers, sample_every)
             res.rce = run.yield_values("cut", 0)
             res.rbn = run.yield_values("nb", 0)
+            self._read_heat(run, res)
         run.close()
         return res
 
@@ -937,9 +938,25 @@ class MarkovChain:
                                       "gap_sum": int(es["gap_sum"][0, e]),
                                       "tally_sum": es["tally_sum"][0][:, [ja, jb]].copy()}
 
+    def _read_heat(self, run, res: "ChainResult", only_dwell: bool = False) -> None:
+        """Chain 0's heat maps over the window, replayed from the event log:
+        ``res.dwell``, and for a logged ReCom run (which keeps no fused tallies) the histograms,
+        ``cut_times`` and the corrected per-node statistics too."""
+        sp = self.cspec.spec
+        hs = run.heat_series(0, 1, want=("dwell",) if only_dwell else run.HEAT_OUTPUTS)
+        res.dwell = hs["dwell"][0].copy()
+        if only_dwell:
+            return
+        res.cut_hist, res.nb_hist = hs["cut_hist"][0].copy(), hs["nb_hist"][0].copy()
+        res.cut_times = {(sp.nodes[u], sp.nodes[v]): int(hs["cut_times"][0, i]) for i, (u, v) in enumerate(self.edges)}
+        occ = res.dwell @ np.asarray(run.cfg.labels, dtype=np.int64)
+        res.flip_count = {sp.nodes[i]: int(hs["moves"][0, i]) for i in range(sp.n)}
+        res.last_accept = {sp.nodes[i]: int(hs["last_move"][0, i]) for i in range(sp.n)}
+        res.occupancy = {sp.nodes[i]: int(occ[i]) for i in range(sp.n)}
+
     # ---- fast path -------------------------------------------------------------------
     def run(self, series: bool = True, frame: Optional[str] = "auto", corrected: bool = True,
-            sample_every: Optional[int] = None, move_cap=None) -> "ChainResult":
+            sample_every: Optional[int] = None, move_cap=None, dwell: bool = False) -> "ChainResult":
         """All ``total_steps`` yields on the device; the reference driver's outputs
         (``grid_chain_sec11.py:366-419``) come back as a :class:`ChainResult`.
 
@@ -952,15 +969,19 @@ class MarkovChain:
         Rao-Blackwellised ``waits_expected``.  ``sample_every`` (a positive integer) keeps the
         plans at yields 0, every, 2 every, ... -- the states ``enumerate(chain)`` reaches at
         ``i % every == 0`` -- in ``ChainResult.plans``, replayed on the device from the event log
-        (DESIGN.md §5f).
+        (DESIGN.md §5f).  ``dwell=True`` keeps the event log and adds ``ChainResult.dwell``, the
+        yields each node spends in each district.
 
         A ``partial(recom, ...)`` chain returns its final state, counters and sums.  With
         ``move_cap`` (ReCom chains only: a positive integer, the moved nodes the log holds, or
         ``"auto"`` = ``(total_steps - 1) * n``, which always suffices) the run logs every accepted
         step's moved nodes (DESIGN.md "ReCom move log"), and the result also carries ``rce`` /
         ``rbn``, ``elections`` / ``shapes`` / ``splits`` from the initial state's updaters and,
-        with ``sample_every``, ``plans``, each exactly as a flip chain fills it.  Without
-        ``move_cap`` a ReCom chain ignores those updaters and refuses ``sample_every``."""
+        with ``sample_every``, ``plans``, each exactly as a flip chain fills it, and the heat maps
+        of the heat-map series: ``cut_hist`` / ``nb_hist``, ``cut_times``,
+        ``flip_count`` (the accepted steps that moved a node), ``last_accept``, ``occupancy`` and
+        ``dwell``; the quirk forms ``num_flips`` / ``part_sum`` / ``last_flipped`` stay empty.
+        Without ``move_cap`` a ReCom chain ignores those updaters and refuses ``sample_every``."""
         recom_chain = self.cspec.proposal == _lib.FC_PROPOSE_RECOM
         if sample_every is not None:
             if isinstance(sample_every, bool) or not isinstance(sample_every, (int, np.integer)) or sample_every < 1:
@@ -968,6 +989,9 @@ class MarkovChain:
             if recom_chain and move_cap is None:
                 raise ValueError("sample_every on a ReCom chain needs its move log: pass move_cap "
                                  "(a capacity in moved nodes, or \"auto\")")
+        if dwell and recom_chain and move_cap is None:
+            raise ValueError("dwell on a ReCom chain needs its move log: pass move_cap "
+                             "(a capacity in moved nodes, or \"auto\")")
         if move_cap is not None:
             if not recom_chain:
                 raise ValueError("move_cap is for ReCom chains: a flip chain sizes its event log itself")
@@ -986,7 +1010,8 @@ class MarkovChain:
                 neg = any(isinstance(nd, tuple) and nd[1] < 0 for nd in self.cspec.spec.nodes)
                 frame = "frank" if neg else "sec11"
         readers = self._series_updaters()
-        log = series or bool(readers[0]) or readers[1] is not None or readers[2] is not None or sample_every is not None
+        log = series or bool(readers[0]) or readers[1] is not None or readers[2] is not None or \
+            sample_every is not None or bool(dwell)
         if log:
             diag |= _lib.FC_DIAG_SERIES
         if corrected:
@@ -997,6 +1022,8 @@ class MarkovChain:
             run.steps(self.total_steps - 1)
         res = ChainResult.from_run(self, run, 0)
         self._read_series_updaters(run, res, readers, sample_every)
+        if dwell:
+            self._read_heat(run, res, only_dwell=True)
         if corrected:
             sp = self.cspec.spec
             xf, xo, xl = run.flips_exact()
@@ -1073,6 +1100,9 @@ class ChainResult:
     # [m], assignment [m, n] int8 district indices (canonical node order, parts in label order), cut,
     # nb, dist0 [m] (|cut|, |B|, Hamming distance to the initial plan), pops [m, k]
     plans: Optional[Dict[str, np.ndarray]] = None
+    # the yields each node spends in each district, [n, k] int64 (canonical node order, parts in
+    # label order), replayed from the event log: a logged ReCom run, or run(dwell=True)
+    dwell: Optional[np.ndarray] = None
     _chain: Any = field(default=None, repr=False, compare=False)  # the chain sampled() views the plans through
 
     def sampled(self):

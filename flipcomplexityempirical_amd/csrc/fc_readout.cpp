@@ -952,6 +952,124 @@ int fc_run_sample_plans_ms(fc_run *r, float *kernel_ms, float *copy_ms) {
     return FC_OK;
 }
 
+// ---- heat-map series (fc_heat.h, fc_heat.hip) -----------------------------------
+
+int fc_run_heat_series(fc_run *r, int32_t c0, int32_t nc, uint32_t flags, int64_t *cut_hist, int64_t *nb_hist,
+                       int64_t *cut_times, int64_t *moves, int64_t *last_move, int64_t *dwell) {
+    const char *const who = "fc_run_heat_series";
+    if (!r) return fail(FC_ERR_ARG, "fc_run_heat_series: null run");
+    CallRules rules;
+    rules.log_pass = "the heat-map series";
+    if (int rc = check_series_call(r, who, c0, nc, rules)) return rc;
+    if (flags & ~(uint32_t)FC_HEAT_LDS_ROWS) return fail(FC_ERR_ARG, "fc_run_heat_series: unknown flags");
+    if (nc == 0) return FC_OK;
+    SeriesCall s;
+    if (int rc = open_window(r, who, c0, nc, true, s)) return rc;
+    const int32_t n = r->g.n, k = r->p.k, E = r->g.n_edges, nbw = r->nb_w;
+    int64_t *const host[fc::kHeatArrays] = {cut_hist, nb_hist, cut_times, moves, last_move, dwell};
+    const size_t cn = (size_t)nc;
+    size_t len[fc::kHeatArrays], total = 0;
+    uint32_t mask = 0;
+    for (int a = 0; a < fc::kHeatArrays; ++a) {
+        len[a] = host[a] ? cn * fc::heat_row_len(a, n, k, E, nbw) : 0;
+        total += len[a];
+        if (host[a]) mask |= 1u << a;
+    }
+    if (!mask) return FC_OK;
+    int q;
+    // the outputs are kept by the run; a larger call has to fit a tenth of the free device memory
+    if (total > r->d_ser_out.capacity()) {
+        size_t free_b = 0, total_b = 0;
+        HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+        if (total * 8 > free_b / 10)
+            return fail(FC_ERR_ARG, "fc_run_heat_series: " + std::to_string(total * 8) + " bytes of outputs (" +
+                                        std::to_string(nc) + " chains) exceed a tenth of the free device memory; " +
+                                        "split the call by chains");
+    }
+    // the neighbour / edge rows and the device's LDS limit: once per run
+    if (!r->ht_width) {
+        const int32_t W = fc::shapes_row_width(r->g.max_degree);
+        if (W == 0) return fail(FC_ERR_UNSUPPORTED, "fc_run_heat_series: node degree above 16");
+        std::vector<fc::HeatSlot> rows;
+        fc::heat_build_rows(n, E, r->g.eu.data(), r->g.ev.data(), W, rows);
+        if ((q = r->d_ht_rows.upload(rows))) return q;
+        int dev = 0, optin = 0;
+        if (hipGetDevice(&dev) != hipSuccess ||
+            hipDeviceGetAttribute(&optin, hipDeviceAttributeSharedMemPerBlockOptin, dev) != hipSuccess || optin <= 0)
+            optin = 65536;
+        r->ht_optin = optin;
+        r->ht_width = W;
+    }
+    const size_t image = fc::heat_lds_bytes(r->npad, n, k, E, nbw, r->ht_width, mask);
+    // the global-rows form unless the LDS form is asked for and the image fits (with one
+    // workgroup per compute unit the LDS form measured slower)
+    const int32_t form =
+        (flags & FC_HEAT_LDS_ROWS) && image <= (size_t)r->ht_optin ? fc::kHeatFormLds : fc::kHeatFormGlobal;
+    // the chains' |cut| and |B| at the window start (open_window has left the run idle)
+    std::vector<int64_t> in(2 * cn);
+    for (int32_t i = 0; i < nc; ++i) {
+        in[i] = s.sc[i].ser_cut0;
+        in[cn + i] = s.sc[i].ser_nb0;
+    }
+    if ((q = r->d_ht_in.grow(in.size()))) return q;
+    HIP_TRY(hipMemcpy(r->d_ht_in, in.data(), in.size() * 8, hipMemcpyHostToDevice));
+    OutPack out;
+    if ((q = out.reserve(r, {len[0], len[1], len[2], len[3], len[4], len[5]}))) return q;
+    fc::HeatParams hp{};
+    hp.log = s.log;
+    hp.rows = r->d_ht_rows;
+    hp.width = r->ht_width;
+    hp.n_edges = E;
+    hp.nb_width = nbw;
+    hp.cut0 = r->d_ht_in;
+    hp.nb0 = r->d_ht_in + cn;
+    hp.cut_hist = cut_hist ? out.at(0) : nullptr;
+    hp.nb_hist = nb_hist ? out.at(1) : nullptr;
+    hp.cut_times = cut_times ? out.at(2) : nullptr;
+    hp.moves = moves ? out.at(3) : nullptr;
+    hp.last_move = last_move ? out.at(4) : nullptr;
+    hp.dwell = dwell ? out.at(5) : nullptr;
+    for (hipEvent_t &ev : r->ht_ev)
+        if (!ev) HIP_TRY(hipEventCreate(&ev));
+    r->ht_form = -1;
+    HIP_TRY(hipEventRecord(r->ht_ev[0], r->stream));
+    const int e = fc::launch_heat(hp, form, r->stream);
+    if (e) return fail(FC_ERR_HIP, std::string("heat-map series: ") + hipGetErrorString((hipError_t)e));
+    HIP_TRY(hipEventRecord(r->ht_ev[1], r->stream));
+    if (int rc = out.fetch(r, {cut_hist, nb_hist, cut_times, moves, last_move, dwell})) return rc;
+    r->ht_form = form;
+    r->ht_lds = (int64_t)(form == fc::kHeatFormLds ? image : fc::heat_base_bytes(r->npad, r->ht_width));
+    return FC_OK;
+}
+
+int fc_run_heat_series_info(fc_run *r, int32_t *form, int64_t *lds_bytes, float *kernel_ms) {
+    if (!r) return fail(FC_ERR_ARG, "fc_run_heat_series_info: null run");
+    if (r->ht_form < 0) return fail(FC_ERR_ARG, "fc_run_heat_series_info: no fc_run_heat_series call recorded");
+    if (form) *form = r->ht_form;
+    if (lds_bytes) *lds_bytes = r->ht_lds;
+    if (kernel_ms) HIP_TRY(hipEventElapsedTime(kernel_ms, r->ht_ev[0], r->ht_ev[1]));
+    return FC_OK;
+}
+
+int fc_graph_heat_rows(const fc_graph *g, int32_t *width, int32_t *nbr, int32_t *eid) {
+    if (!g || !width) return fail(FC_ERR_ARG, "fc_graph_heat_rows: null argument");
+    fc_graph_info gi;
+    if (int rc = fc_graph_get_info(g, &gi)) return rc;
+    const int32_t W = fc::shapes_row_width(gi.max_degree);
+    if (W == 0) return fail(FC_ERR_UNSUPPORTED, "fc_graph_heat_rows: node degree above 16");
+    *width = W;
+    if (!nbr && !eid) return FC_OK;
+    std::vector<int32_t> eu((size_t)gi.n_edges + 1), ev((size_t)gi.n_edges + 1);
+    if (int rc = fc_graph_edges(g, eu.data(), ev.data())) return rc;
+    std::vector<fc::HeatSlot> rows;
+    fc::heat_build_rows(gi.n_nodes, gi.n_edges, eu.data(), ev.data(), W, rows);
+    for (size_t i = 0; i < rows.size(); ++i) {
+        if (nbr) nbr[i] = rows[i].nbr;
+        if (eid) eid[i] = rows[i].eid;
+    }
+    return FC_OK;
+}
+
 int fc_run_read_hist(fc_run *r, int64_t *cut_hist, int64_t *nb_hist) {
     if (!r || !cut_hist || !nb_hist) return fail(FC_ERR_ARG, "fc_run_read_hist: null argument");
     if (!r->d_cut_hist) return fail(FC_ERR_ARG, "fc_run_read_hist: FC_DIAG_HIST not enabled");

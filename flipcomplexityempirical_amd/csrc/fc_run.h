@@ -8,6 +8,7 @@
 #include <utility>
 #include <vector>
 
+#include "fc_heat.h"
 #include "fc_internal.h"
 #include "fc_ladder.h"
 #include "fc_plan.h"
@@ -181,6 +182,15 @@ struct fc_run : fc::RunShape {
     DevBuf<int32_t> d_pl_pop;     // [npad] node populations, 0 beyond n (uploaded by the first call with pops)
     hipEvent_t pl_ev[3] = {nullptr, nullptr, nullptr};  // last call: before the kernel, after it, after the row copy
     bool pl_timed = false, pl_copied = false;           // (fc_run_sample_plans_ms)
+    // heat-map series (fc_run_heat_series; fc_heat.h, fc_heat.hip): no setter; the neighbour / edge rows
+    // are built and uploaded by the first call and kept, like the frame tables.  ht_width 0: not yet
+    int32_t ht_width = 0;
+    int32_t ht_optin = 0;         // the device's opt-in dynamic LDS limit, queried by the first call
+    DevBuf<fc::HeatSlot> d_ht_rows;  // [n * ht_width]
+    DevBuf<int64_t> d_ht_in;      // per call: series_cut0 and series_nb0 [nc] each
+    hipEvent_t ht_ev[2] = {nullptr, nullptr};  // last call: before the kernel, after it
+    int32_t ht_form = -1;         // last call that launched: fc::kHeatFormLds / kHeatFormGlobal (-1: none yet)
+    int64_t ht_lds = 0;           // ... and the dynamic LDS bytes of its workgroups
     char kname[96] = {0};       // last launched flip-kernel instance
     // replica exchange (fc_run_set_ladders; fc_ladder.h, fc_exchange.hip).  Slots are flat: ladder
     // l's rung r is slot lad_off[l] + r
@@ -200,6 +210,8 @@ struct fc_run : fc::RunShape {
     ~fc_run() {
         for (auto &pr : launch_events) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
         for (hipEvent_t e : pl_ev)
+            if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : ht_ev)
             if (e) (void)hipEventDestroy(e);
         if (stream) (void)hipStreamDestroy(stream);
     }

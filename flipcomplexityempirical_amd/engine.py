@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import ctypes
 from dataclasses import dataclass
-from typing import Dict, Optional, Sequence
+from typing import Any, Dict, Optional, Sequence
 
 import numpy as np
 
@@ -99,6 +99,19 @@ class FlipGraph:
         meta = np.zeros(self.n, dtype=np.uint64)
         check(_lib.load().fc_graph_rings(self.handle, _p(ring, ctypes.c_int32), _p(meta, ctypes.c_uint64)))
         return ring.reshape(self.n, R), meta
+
+    def heat_rows(self):
+        """``(nbr, eid)``, ``[n, width]`` each: the neighbour / edge rows the heat-map replay walks
+        (``fc_graph_heat_rows``; host code, no device): slot j of node u holds a neighbour and the
+        canonical id of the edge to it, -1 / -1 when empty."""
+        L = _lib.load()
+        width = ctypes.c_int32(0)
+        check(L.fc_graph_heat_rows(self.handle, ctypes.byref(width), None, None), "fc_graph_heat_rows")
+        nbr = np.zeros(self.n * width.value, dtype=np.int32)
+        eid = np.zeros(self.n * width.value, dtype=np.int32)
+        check(L.fc_graph_heat_rows(self.handle, ctypes.byref(width), _p(nbr, ctypes.c_int32), _p(eid, ctypes.c_int32)),
+              "fc_graph_heat_rows")
+        return nbr.reshape(self.n, width.value), eid.reshape(self.n, width.value)
 
     def close(self):
         if getattr(self, "handle", None):
@@ -728,6 +741,44 @@ class FlipRun:
         check(_lib.load().fc_run_sample_plans_ms(self.handle, ctypes.byref(k_ms), ctypes.byref(c_ms)),
               "fc_run_sample_plans_ms")
         return float(k_ms.value), float(c_ms.value)
+
+    # ---- heat-map series ----------------------------------------------
+    HEAT_OUTPUTS = ("cut_hist", "nb_hist", "cut_times", "moves", "last_move", "dwell")
+
+    def heat_series(self, c0: int = 0, nc: Optional[int] = None, want: Sequence[str] = HEAT_OUTPUTS,
+                    lds_rows: bool = False) -> Dict[str, np.ndarray]:
+        """The heat maps of chains ``c0 .. c0 + nc - 1`` over the series window, replayed on the
+        device from the event log (``fc_run_heat_series``; include/flipchain.h): ``cut_hist``
+        ``[nc, E + 1]`` and ``nb_hist`` ``[nc, nb_width]`` (yields per |cut| and |B|), ``cut_times``
+        ``[nc, E]`` (yields each canonical edge is cut), ``moves`` / ``last_move`` ``[nc, n]``
+        (logged events on each node and the yield of the last), ``dwell`` ``[nc, n, k]`` (yields each
+        node spends in each district) and ``yields`` ``[nc]``, all int64.  ``want`` names the
+        outputs to compute (the others are left out).  The replay accumulates in the output rows in
+        device memory; ``lds_rows`` keeps a chain's arrays in LDS instead when they fit (same
+        output, slower as measured; :meth:`heat_series_info` tells which form ran).  Flip runs of
+        any k and ReCom runs with a move log."""
+        unknown = [key for key in want if key not in self.HEAT_OUTPUTS]
+        if unknown:
+            raise ValueError(f"heat_series: unknown outputs {unknown} (known: {', '.join(self.HEAT_OUTPUTS)})")
+        n, k = self.graph.n, self.cfg.k
+        shapes = {"cut_hist": (self.graph.n_edges + 1,), "nb_hist": (self.nb_width(),),
+                  "cut_times": (self.graph.n_edges,), "moves": (n,), "last_move": (n,), "dwell": (n, k)}
+        nc = self.n_chains - c0 if nc is None else int(nc)
+        out = {key: np.zeros((max(nc, 0),) + shapes[key], dtype=np.int64) for key in self.HEAT_OUTPUTS if key in want}
+        check(_lib.load().fc_run_heat_series(self.handle, int(c0), nc, _lib.FC_HEAT_LDS_ROWS if lds_rows else 0,
+                                             *(_p(out.get(key), ctypes.c_int64) for key in self.HEAT_OUTPUTS)),
+              "fc_run_heat_series")
+        st = self.stats()
+        out["yields"] = (st["steps"] - st["series_t0"] + 1)[c0:c0 + nc].astype(np.int64)
+        return out
+
+    def heat_series_info(self) -> Dict[str, Any]:
+        """The last :meth:`heat_series` call that launched (``fc_run_heat_series_info``): ``form``
+        ("lds" or "global_rows"), ``lds_bytes`` of one workgroup and the kernel's device ``ms``."""
+        form, lds, ms = ctypes.c_int32(-1), ctypes.c_int64(0), ctypes.c_float(0)
+        check(_lib.load().fc_run_heat_series_info(self.handle, ctypes.byref(form), ctypes.byref(lds), ctypes.byref(ms)),
+              "fc_run_heat_series_info")
+        return {"form": "lds" if form.value == 0 else "global_rows", "lds_bytes": int(lds.value), "ms": float(ms.value)}
 
     # ---- replica exchange (DESIGN.md "Replica exchange") ------------------------------
     def set_ladders(self, ladders: Sequence[Sequence[int]], hist: bool = False) -> "FlipRun":

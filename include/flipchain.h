@@ -358,7 +358,7 @@ int fc_run_read_wait_expected(fc_run *r, double *out);
 /* The event log and every pass below serve flip runs and ReCom runs alike.  A ReCom run created
  * with FC_DIAG_SERIES and an event_cap keeps a move log (the kernel instance fc::recom_log_kernel);
  * one created without answers FC_ERR_UNSUPPORTED to the setters and series calls of the election,
- * compactness, locality-splits and plan-sample sections (create it with FC_DIAG_SERIES and an
+ * compactness, locality-splits, plan-sample and heat-map sections (create it with FC_DIAG_SERIES and an
  * event_cap), and FC_ERR_ARG to fc_run_read_events and fc_run_autocorr, like any run without a log.
  * The burst convention: several events may share one t (the nodes one ReCom step moves), and
  *   a_t = the window-start assignment with every event of t_e <= t applied,
@@ -587,6 +587,62 @@ int fc_run_sample_plans(fc_run *r, int32_t c0, int32_t nc, int32_t n_times, cons
  * the kernel, and the copy of the plan rows to the host (0 when plans was NULL).  Either may be
  * NULL.  FC_ERR_ARG before the first such call. */
 int fc_run_sample_plans_ms(fc_run *r, float *kernel_ms, float *copy_ms);
+/* ---- heat-map series: the reference's main outputs (per-edge cut_times :383-384, per-node flip
+ * counts and label integrals :396-400, the histograms of len(cut_edges) and len(b_nodes)) over the
+ * series window, by a device replay of the event log.  Flip runs of any k, and
+ * ReCom runs with a move log (above), with FC_DIAG_SERIES; no setter, nothing kept between calls
+ * (the run keeps the neighbour / edge rows it builds on the first call).  The window's yields are
+ * t = series_t0 .. steps, both inclusive;
+ *   a_t = the window-start assignment with every logged event of t_e <= t applied in log order.
+ * Per chain, edges in fc_graph_edges order, all exact int64:
+ *   cut_hist[x]   = yields with |cut| = x, x = 0..E;   nb_hist[x] = the same for |B|,
+ *                   x = 0..fc_run_nb_width - 1.  |cut| and |B| at yield t are those of the last
+ *                   event with t_e <= t, and series_cut0 / series_nb0 when there is none; each row
+ *                   sums to the window's yields;
+ *   cut_times[e]  = yields with a_t(eu[e]) != a_t(ev[e]);
+ *   moves[u]      = logged events on u: the accepted flips of u (flip runs), the accepted steps
+ *                   that moved u (ReCom runs); either way the yields t of the window with
+ *                   a_t(u) != a_{t-1}(u);
+ *   last_move[u]  = t of the last event on u, 0 when there is none (last_accept's convention;
+ *                   events have t >= 1);
+ *   dwell[u][d]   = yields with a_t(u) = d; every node's row sums to the window's yields.
+ * Over a window from yield 0 of a flip run, cut_hist / nb_hist are fc_run_read_hist's rows,
+ * cut_times fc_run_read_edges', moves and last_move fc_run_read_flips_exact's flip_count and
+ * last_accept, and sum_d labels[d] dwell[u][d] its occupancy; ReCom runs have no other source
+ * of them.
+ *
+ * Any output may be NULL to skip it; nc = 0 is FC_OK and writes nothing; the call synchronises.
+ * The replay accumulates in the output rows in device memory (the global-rows form, the default: a
+ * chain's workgroup then needs little LDS and many chains share a compute unit, which measured 4.7
+ * times faster on the C2 shape).  Under FC_HEAT_LDS_ROWS it keeps every requested
+ * array of a chain in LDS beside its assignment and writes them out once at the end (the LDS form),
+ * when that image fits the device's opt-in dynamic LDS limit (queried); an image that does not fit
+ * takes the global-rows form all the same.  Same output either way.  There is no LDS refusal: every
+ * n a logged run admits is supported.  FC_ERR_ARG without FC_DIAG_SERIES, for a bad chain
+ * range, unknown flags, a window of 2^30 yields or more, a chain whose log overflowed event_cap
+ * (the message names the chain), or when the requested outputs exceed a tenth of the free device
+ * memory: split the call by chains.  FC_ERR_UNSUPPORTED for ReCom runs without a move log.  Calls
+ * interleave freely with the other series calls and with other chain ranges; checkpoint blobs are
+ * byte for byte what they were. */
+#define FC_HEAT_LDS_ROWS 0x1u    /* privatise the requested arrays in LDS when the chain's image fits,
+                                    instead of accumulating in the output rows in device memory
+                                    (test / measurement knob: the slower form as measured)        */
+int fc_run_heat_series(fc_run *r, int32_t c0, int32_t nc, uint32_t flags,
+                       int64_t *cut_hist,    /* [nc * (E + 1)]                       */
+                       int64_t *nb_hist,     /* [nc * nb_width]  (fc_run_nb_width)   */
+                       int64_t *cut_times,   /* [nc * E]                             */
+                       int64_t *moves,       /* [nc * n]                             */
+                       int64_t *last_move,   /* [nc * n]                             */
+                       int64_t *dwell);      /* [nc * n * k]                         */
+/* The last fc_run_heat_series call that launched: *form = 0 the LDS form, 1 the global-rows form;
+ * *lds_bytes = the dynamic LDS of one of its workgroups; *kernel_ms = the kernel's device time
+ * (HIP events on the run's stream).  Any may be NULL.  FC_ERR_ARG before the first such call. */
+int fc_run_heat_series_info(fc_run *r, int32_t *form, int64_t *lds_bytes, float *kernel_ms);
+/* The neighbour / edge rows the heat-map replay walks, by the code that builds them: *width = slots
+ * per row (8 or 16); nbr / eid [n * width]: slot j of node u holds a neighbour and the canonical id
+ * (fc_graph_edges order) of the edge to it, -1 / -1 when empty.  nbr and eid may be NULL (width
+ * only).  Pure host function; FC_ERR_UNSUPPORTED for a node degree above 16. */
+int fc_graph_heat_rows(const fc_graph *g, int32_t *width, int32_t *nbr, int32_t *eid);
 /* Page-lock (pin) a caller's host buffer for faster device-to-host copies of the readers above
  * (hipHostRegister); unregister before freeing it. */
 int fc_host_register(void *ptr, int64_t bytes);
