@@ -53,6 +53,33 @@ __device__ __forceinline__ int64_t wave_sum64(int64_t x) {
     return x;
 }
 
+// x of the lane a DPP control pairs this one with (every lane has a partner under these controls)
+template <int CTRL>
+__device__ __forceinline__ int32_t dpp_pair(int32_t x) {
+    return __builtin_amdgcn_update_dpp(x, x, CTRL, 0xf, 0xf, false);
+}
+constexpr int kQuadSwap1 = 0xB1;     // quad_perm [1, 0, 3, 2]
+constexpr int kQuadSwap2 = 0x4E;     // quad_perm [2, 3, 0, 1]
+constexpr int kRowHalfMirror = 0x141;
+constexpr int kRowMirror = 0x140;
+
+// the sum of x over lanes 0 .. 15 (wave-uniform)
+__device__ __forceinline__ int32_t row0_sum(int32_t x) {
+    x += dpp_pair<kQuadSwap1>(x);
+    x += dpp_pair<kQuadSwap2>(x);
+    x += dpp_pair<kRowHalfMirror>(x);
+    x += dpp_pair<kRowMirror>(x);
+    return rl32(x, 0);
+}
+// the minimum of x over lanes 0 .. 31 (wave-uniform)
+__device__ __forceinline__ int32_t min_lanes32(int32_t x) {
+    x = min(x, dpp_pair<kQuadSwap1>(x));
+    x = min(x, dpp_pair<kQuadSwap2>(x));
+    x = min(x, dpp_pair<kRowHalfMirror>(x));
+    x = min(x, dpp_pair<kRowMirror>(x));
+    return min(rl32(x, 0), rl32(x, 16));
+}
+
 __device__ __forceinline__ int count_below(uint64_t m) {  // set bits of m below this lane
     return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
 }

@@ -1,7 +1,8 @@
 // Heat-map series: the parameters of the kernel that replays the FC_DIAG_SERIES
 // event logs into the reference's heat maps over the series window (fc_heat.hip) -- the |cut| and
 // |B| histograms, per-edge cut times, per-node move counts, last moves and district dwell times --
-// the layout of a chain's image, and the host-built neighbour / edge rows the kernel walks.
+// and the layout of a chain's image.  The neighbour / edge rows the kernel walks are fc_replay.h's
+// (build_rows with the edge's canonical id as the value, -1 in an empty slot).
 //
 // a_t is the window-start assignment with every logged event of t_e <= t applied in log order.
 // Every per-edge and per-node integral is kept lazily (DESIGN.md §4 "cut_times"): an event at
@@ -11,8 +12,6 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
-
-#include <vector>
 
 #include "fc_philox.h"  // FC_HD
 #include "fc_replay.h"
@@ -26,17 +25,11 @@ constexpr int kHeatArrays = 6;
 // The accumulation forms (fc_run_heat_series_info)
 constexpr int32_t kHeatFormLds = 0, kHeatFormGlobal = 1;
 
-// A slot of a node's neighbour row: the neighbour's id (-1: empty) and the canonical id of the
-// edge to it
-struct alignas(8) HeatSlot {
-    int32_t nbr, eid;
-};
-
 // Kernel parameters (passed by value).  Output rows are per chain of the call, [nc] rows each; a
 // null output is skipped.
 struct HeatParams {
     LogWindow log;             // the chains read and their window (fc_replay.h)
-    const HeatSlot *rows;      // [n * width] neighbour rows
+    const RowSlot *rows;       // [n * width] neighbour rows: the edge's canonical id, -1 in an empty slot
     int32_t width;             // slots per row: 8 or 16
     int32_t n_edges;           // E
     int32_t nb_width;          // entries of an |B| histogram row
@@ -57,7 +50,7 @@ FC_HD size_t heat_row_len(int a, int32_t n, int32_t k, int32_t n_edges, int32_t 
 // LDS bytes of the part both forms keep: the chunk's neighbour rows [64][width] and the current
 // assignment (npad is a multiple of 16)
 FC_HD size_t heat_base_bytes(int32_t npad, int32_t width) {
-    return sizeof(HeatSlot) * 64 * (size_t)width + (((size_t)npad + 15) & ~(size_t)15);
+    return sizeof(RowSlot) * 64 * (size_t)width + (((size_t)npad + 15) & ~(size_t)15);
 }
 // LDS bytes of a chain's image in the LDS form: the base, then every requested array (mask) in
 // the entry point's order, each padded to 16 bytes
@@ -67,19 +60,6 @@ FC_HD size_t heat_lds_bytes(int32_t npad, int32_t n, int32_t k, int32_t n_edges,
     for (int a = 0; a < kHeatArrays; ++a)
         if ((mask >> a) & 1u) b += (8 * heat_row_len(a, n, k, n_edges, nb_width) + 15) & ~(size_t)15;
     return b;
-}
-
-// The neighbour rows: every canonical edge e = (eu[e], ev[e]) in the rows of both its ends, in
-// edge order (width >= the maximum degree).  HIP-free host code.
-inline void heat_build_rows(int32_t n, int32_t n_edges, const int32_t *eu, const int32_t *ev, int32_t width,
-                            std::vector<HeatSlot> &rows) {
-    rows.assign((size_t)n * width, HeatSlot{-1, -1});
-    std::vector<int32_t> fill((size_t)n, 0);
-    for (int32_t e = 0; e < n_edges; ++e) {
-        const int32_t u = eu[e], w = ev[e];
-        rows[(size_t)u * width + fill[u]++] = HeatSlot{w, e};
-        rows[(size_t)w * width + fill[w]++] = HeatSlot{u, e};
-    }
 }
 
 // One 64-thread workgroup per chain of [c0, c0 + nc); `form` kHeatFormLds needs

@@ -26,8 +26,8 @@
 // measured 4.7 times slower on the C2 shape.
 #include <hip/hip_runtime.h>
 
-#include "fc_device.h"
 #include "fc_heat.h"
+#include "fc_replay_dev.h"
 
 namespace fc {
 namespace {
@@ -43,14 +43,14 @@ __device__ __forceinline__ void add(u64 *p, int64_t x) { (void)atomicAdd(p, (u64
 template <int W, bool LDS>
 __global__ __launch_bounds__(64) void heat_kernel(const HeatParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int RV = W / 2;  // 16-byte pieces of a row
+    using NbrRows = replay::Rows<W>;
+    constexpr int RV = NbrRows::RV;  // 16-byte pieces of a row
     const int lane = (int)threadIdx.x;
     const int32_t cl = (int32_t)blockIdx.x;
     const LogWindow &w = p.log;
     const int32_t c = w.c0 + cl;
     const int32_t k = w.k, n = w.n, E = p.n_edges, nbw = p.nb_width;
     int4 *stage4 = (int4 *)smem;                 // [64][W] the chunk's neighbour rows
-    const HeatSlot *stage = (const HeatSlot *)stage4;
     int8_t *cur = (int8_t *)(stage4 + 64 * RV);  // [npad]
     const int nvec = (w.npad + 15) / 16;
 
@@ -117,37 +117,18 @@ __global__ __launch_bounds__(64) void heat_kernel(const HeatParams p) {
     };
     close(-t0);
 
-    const ulonglong2 *ev = (const ulonglong2 *)(w.events + (size_t)c * w.ev_cap);
-    const int64_t ne = w.ev_len[cl] < w.ev_cap ? w.ev_len[cl] : w.ev_cap;
-    // this lane's event of log index idx: its node (-1: none) and target
-    auto decode = [&](const ulonglong2 &e, int64_t idx, int &v, int &tg) {
-        v = (int)(e.y & 0xffffu);
-        tg = (int)((e.y >> 48) & 0xffu);
-        if (!(idx < ne && v < n && tg < k)) {
-            v = -1;
-            tg = 0;
-        }
-    };
-    auto load_row = [&](int v, int4 (&r)[RV]) {
-#pragma unroll
-        for (int q = 0; q < RV; ++q) r[q] = make_int4(-1, -1, -1, -1);
-        if (v >= 0) {
-            const int4 *row = (const int4 *)(p.rows + (size_t)v * W);
-#pragma unroll
-            for (int q = 0; q < RV; ++q) r[q] = row[q];
-        }
-    };
-    // the events of the next chunk and of the one after it, and the next chunk's rows
-    ulonglong2 e1 = {0ull, 0ull}, e2 = {0ull, 0ull};
-    if (lane < ne) e1 = ev[lane];
-    if (64 + lane < ne) e2 = ev[64 + lane];
+    const replay::Log log(w, cl);
+    const int64_t ne = log.ne;
+    // the events of the next chunk and of the one after it, and the next chunk's rows (empty
+    // slots: edge -1)
+    replay::Prefetch<2> nx(log, lane);
     int v1, tg1;
-    decode(e1, lane, v1, tg1);
+    replay::decode(nx.e[0], lane < ne, n, k, v1, tg1);
     int4 r1[RV];
-    load_row(v1, r1);
+    NbrRows::load(p.rows, v1, -1, r1);
     // the window-start |cut| and |B| hold until the first event
     {
-        const int64_t t_first = ne > 0 ? rl64((int64_t)e1.x, 0) : t_end;
+        const int64_t t_first = ne > 0 ? rl64(replay::ev_t(nx.e[0]), 0) : t_end;
         const int64_t c0v = p.cut0[cl], b0v = p.nb0[cl];
         if (lane == 0 && t_first > t0) {
             if (h_cut && c0v >= 0 && c0v <= E) add(&cut_hist[c0v], t_first - t0);
@@ -156,20 +137,17 @@ __global__ __launch_bounds__(64) void heat_kernel(const HeatParams p) {
     }
 
     for (int64_t base = 0; base < ne; base += 64) {
-        const int64_t t = (int64_t)e1.x;
+        const int64_t t = replay::ev_t(nx.e[0]);
         const int v = v1, tg = tg1;
-        const int ecut = (int)((e1.y >> 16) & 0xffffu), enb = (int)((e1.y >> 32) & 0xffffu);
+        const int ecut = replay::ev_cut(nx.e[0]), enb = replay::ev_nb(nx.e[0]);
         const bool in = base + lane < ne;
-#pragma unroll
-        for (int q = 0; q < RV; ++q) stage4[lane * RV + q] = r1[q];
-        e1 = e2;
-        decode(e1, base + 64 + lane, v1, tg1);
-        load_row(v1, r1);
-        e2 = ulonglong2{0ull, 0ull};
-        if (base + 128 + lane < ne) e2 = ev[base + 128 + lane];
+        NbrRows::stage(stage4, lane, r1);
+        replay::decode(nx.e[1], base + 64 + lane < ne, n, k, v1, tg1);
+        NbrRows::load(p.rows, v1, -1, r1);
+        nx.advance(log, base, lane);
         // the histograms: this event's |cut| and |B| hold until the next event's t
         int64_t t_next = (int64_t)__shfl_down((long long)t, 1);
-        const int64_t t_chunk = rl64((int64_t)e1.x, 0);  // the next chunk's first t
+        const int64_t t_chunk = rl64(replay::ev_t(nx.e[0]), 0);  // the next chunk's first t
         if (lane == 63) t_next = t_chunk;
         if (base + lane + 1 >= ne) t_next = t_end;
         if (in && t_next > t) {
@@ -178,7 +156,7 @@ __global__ __launch_bounds__(64) void heat_kernel(const HeatParams p) {
         }
         __syncthreads();
 
-        const int cnt = (int)(ne - base < 64 ? ne - base : 64);
+        const int cnt = log.count(base);
         for (int i = 0; i < cnt; ++i) {
             const int vi = rl32(v, i);
             if (vi < 0) continue;
@@ -186,14 +164,13 @@ __global__ __launch_bounds__(64) void heat_kernel(const HeatParams p) {
             const int td = rl32(tg, i);
             // slot `lane` of the node's row and the neighbour's district now (the row and cur[v]
             // are read together: one LDS latency, then the neighbours')
-            HeatSlot s = HeatSlot{-1, -1};
-            if (lane < W) s = stage[i * W + lane];
+            const RowSlot s = NbrRows::slot(stage4, i, lane, -1);
             const int cv = (int)cur[vi];
             const int dw = s.nbr >= 0 ? (int)cur[s.nbr] : -1;
             const int od = __builtin_amdgcn_readfirstlane(cv);
             if (od != td) {
                 // an edge to the old district turns cut (-t), one to the target turns uncut (+t)
-                if (h_ct && s.nbr >= 0 && (dw == od || dw == td)) add(&ct[s.eid], dw == td ? te : -te);
+                if (h_ct && s.nbr >= 0 && (dw == od || dw == td)) add(&ct[s.val], dw == td ? te : -te);
                 if (h_dw && lane == 16 && od < k) add(&dwell[(size_t)vi * k + od], te);
                 if (h_dw && lane == 17) add(&dwell[(size_t)vi * k + td], -te);
                 if (lane == 18) cur[vi] = (int8_t)td;

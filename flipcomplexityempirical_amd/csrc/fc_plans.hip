@@ -15,32 +15,21 @@
 //
 // The one ordering hazard is several events on one node in one apply step (a flip chain flips the
 // same boundary node back and forth): of the step's lanes with the same node, the highest writes
-// cur[v].  A lane finds those lanes with match_mask, one ballot per bit of the node id; a step of
-// one lane needs no mask.
+// cur[v].  A lane finds those lanes with match_mask (fc_replay_dev.h), one ballot per bit of the
+// node id; a step of one lane needs no mask.
 #include <hip/hip_runtime.h>
 
-#include "fc_device.h"
 #include "fc_plans.h"
+#include "fc_replay_dev.h"
 
 namespace fc {
 namespace {
 
 using dev::rl32;
 using dev::rl64;
+using replay::bits_for;
+using replay::match_mask;
 
-// The lanes of `on` whose key `theirs` equals this lane's key `mine` (both below 2^bits, bits
-// wave-uniform): fc_splits.hip's, kept here as the passes keep their own event decode.  Call with
-// the whole wave active.
-__device__ __forceinline__ uint64_t match_mask(uint32_t mine, uint32_t theirs, int bits, uint64_t on) {
-    uint64_t differ = 0;
-    for (int b = 0; b < bits; ++b) {
-        const uint64_t has = __ballot((theirs >> b) & 1u);
-        differ |= ((mine >> b) & 1u) ? ~has : has;
-    }
-    return ~differ & on;
-}
-// bits that hold every value below x (x >= 1)
-__device__ __forceinline__ int bits_for(int32_t x) { return x <= 1 ? 0 : 32 - __builtin_clz((uint32_t)(x - 1)); }
 // the bytes of x that are not 0
 __device__ __forceinline__ int nonzero_bytes(uint32_t x) {
     return __popc((((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x) & 0x80808080u);
@@ -121,24 +110,23 @@ __global__ __launch_bounds__(64) void plans_kernel(const PlansParams p) {
         __syncthreads();  // every lane has read cur and popk
     };
 
-    const ulonglong2 *ev = (const ulonglong2 *)(w.events + (size_t)ch * w.ev_cap);
-    const int64_t ne = w.ev_len[cl] < w.ev_cap ? w.ev_len[cl] : w.ev_cap;
-    // this lane's event of the next chunk, loaded one chunk ahead
-    ulonglong2 nx = {0ull, 0ull};
-    if (lane < ne) nx = ev[lane];
+    const replay::Log log(w, cl);
+    const int64_t ne = log.ne;
+    replay::Prefetch<1> nx(log, lane);  // this lane's event of the next chunk, loaded one chunk ahead
     int32_t cut_now = (int32_t)p.cut0[cl], nb_now = (int32_t)p.nb0[cl];  // wave-uniform
     int32_t j = 0;
 
     for (int64_t base = 0; j < nT; base += 64) {
-        const int64_t t = (int64_t)nx.x;
-        const int v = (int)(nx.y & 0xffffu), tg = (int)((nx.y >> 48) & 0xffu);
-        const int ecut = (int)((nx.y >> 16) & 0xffffu), enb = (int)((nx.y >> 32) & 0xffffu);
+        const replay::Event e = nx.e[0];
+        const int64_t t = replay::ev_t(e);
+        const int v = replay::ev_node(e), tg = replay::ev_target(e);
+        const int ecut = replay::ev_cut(e), enb = replay::ev_nb(e);
         const bool in = base + lane < ne;
         const uint64_t inm = __ballot(in);
         const uint64_t ok = __ballot(in && v < n && tg < k);  // the lanes that may write cur
-        if (base + 64 + lane < ne) nx = ev[base + 64 + lane];
+        nx.advance(log, base, lane);
         // the next chunk's first t: samples from it on wait for that chunk
-        const int64_t t_next = base + 64 < ne ? rl64((int64_t)nx.x, 0) : INT64_MAX;
+        const int64_t t_next = base + 64 < ne ? rl64(replay::ev_t(nx.e[0]), 0) : INT64_MAX;
         // lanes m (wave-uniform, all of them in `ok`) into cur: of the lanes with one node, the highest
         auto apply = [&](uint64_t m) {
             if (!m) return;

@@ -51,12 +51,13 @@ int check_series_call(const fc_run *r, const char *who, int32_t c0, int32_t nc, 
 struct SeriesCall {
     fc::LogWindow log{};
     std::vector<fc::ChainScalars> sc;  // the scalars of chains [c0, c0 + nc)
+    const int64_t *cut0 = nullptr, *nb0 = nullptr;  // device, [nc]: |cut| and |B| at the window start
 };
 
 // The window of a checked call: the chains' scalars, the per-chain overflow check (and, with
-// bound_yields, a window below 2^30 yields), and ev_len, t0, t_end, indexed by the call-local
-// chain, in r->d_ser_meta.  download_scalars leaves the run idle, so the upload is a blocking copy
-// of pageable memory: the window is on the device when this returns.
+// bound_yields, a window below 2^30 yields), and ev_len, t0, t_end, ser_cut0, ser_nb0, indexed by
+// the call-local chain, in r->d_ser_meta.  download_scalars leaves the run idle, so the upload is
+// a blocking copy of pageable memory: the window is on the device when this returns.
 int open_window(fc_run *r, const char *who, int32_t c0, int32_t nc, bool bound_yields, SeriesCall &s) {
     const std::string w(who);
     s.log = fc::LogWindow{};
@@ -69,7 +70,7 @@ int open_window(fc_run *r, const char *who, int32_t c0, int32_t nc, bool bound_y
     s.log.c0 = c0;
     s.log.nc = nc;
     if (int rc = download_scalars(r, c0, nc, s.sc)) return rc;
-    std::vector<int64_t> meta((size_t)3 * nc);
+    std::vector<int64_t> meta((size_t)5 * nc);
     for (int32_t i = 0; i < nc; ++i) {
         const fc::ChainScalars &x = s.sc[i];
         if (int rc = check_event_overflow(r, who, c0 + i, x)) return rc;
@@ -79,12 +80,25 @@ int open_window(fc_run *r, const char *who, int32_t c0, int32_t nc, bool bound_y
         meta[i] = x.ev_len;
         meta[(size_t)nc + i] = x.ser_t0;
         meta[(size_t)2 * nc + i] = x.steps + 1;
+        meta[(size_t)3 * nc + i] = x.ser_cut0;
+        meta[(size_t)4 * nc + i] = x.ser_nb0;
     }
     if (int rc = r->d_ser_meta.grow(meta.size())) return rc;
     HIP_TRY(hipMemcpy(r->d_ser_meta, meta.data(), meta.size() * 8, hipMemcpyHostToDevice));
     s.log.ev_len = r->d_ser_meta;
     s.log.t0 = r->d_ser_meta + nc;
     s.log.t_end = r->d_ser_meta + 2 * (size_t)nc;
+    s.cut0 = r->d_ser_meta + 3 * (size_t)nc;
+    s.nb0 = r->d_ser_meta + 4 * (size_t)nc;
+    return FC_OK;
+}
+
+// Whether `bytes` more of device memory fit a tenth of what is free: the bound on a buffer that a
+// run keeps and a single call sizes.
+int fits_free_tenth(size_t bytes, bool &fits) {
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    fits = bytes <= free_b / 10;
     return FC_OK;
 }
 
@@ -482,9 +496,9 @@ int fc_run_frame_series_changes(fc_run *r, int32_t c0, int32_t nc, int32_t n_fra
     if (!query && !(r->p.flags & FC_FLAG_SERIES_TWO_PASS)) {
         const size_t want = (size_t)r->n_chains * (size_t)stage_cap;
         if (2 * want > r->d_st_sa.capacity()) {  // (d_st_sa is allocated last: it vouches for d_st_t)
-            size_t free_b = 0, total_b = 0;
-            HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-            if (want * 24 <= free_b / 10) {
+            bool fits = false;
+            if ((q = fits_free_tenth(want * 24, fits))) return q;
+            if (fits) {
                 r->d_st_t.release();  // both go before either comes back
                 r->d_st_sa.release();
                 if ((q = r->d_st_t.grow(want))) return q;
@@ -683,21 +697,16 @@ int fc_run_set_shapes(fc_run *r, const int32_t *node_area, const int32_t *node_e
     if (area > INT32_MAX) return fail(FC_ERR_ARG, "fc_run_set_shapes: node_area totals over 2^31 - 1");
     if (perim > INT32_MAX)
         return fail(FC_ERR_ARG, "fc_run_set_shapes: node_ext and edge_len together total over 2^31 - 1");
-    const int32_t W = fc::shapes_row_width(r->g.max_degree);
+    const int32_t W = fc::row_width(r->g.max_degree);
     if (W == 0) return fail(FC_ERR_UNSUPPORTED, "fc_run_set_shapes: node degree above 16");
     if (!fc::shapes_fit_lds(r->npad, r->p.k, n_pp_edges, W))
         return fail(FC_ERR_UNSUPPORTED,
                     "fc_run_set_shapes: a chain's image (" +
                         std::to_string(fc::shapes_lds_bytes(r->npad, r->p.k, n_pp_edges, W)) +
                         " bytes: assignment, histograms, neighbour rows) does not fit 48 KB of LDS");
-    // the neighbour rows: every canonical edge in the rows of both its ends
-    std::vector<fc::ShapeSlot> rows((size_t)n * W, fc::ShapeSlot{-1, 0});
-    std::vector<int32_t> fill(n, 0);
-    for (int32_t e = 0; e < E; ++e) {
-        const int32_t u = r->g.eu[e], w = r->g.ev[e];
-        rows[(size_t)u * W + fill[u]++] = fc::ShapeSlot{w, edge_len[e]};
-        rows[(size_t)w * W + fill[w]++] = fc::ShapeSlot{u, edge_len[e]};
-    }
+    // the neighbour rows: every canonical edge, with its length, in the rows of both its ends
+    std::vector<fc::RowSlot> rows;
+    fc::build_rows(n, E, r->g.eu.data(), r->g.ev.data(), W, edge_len, 0, rows);
     std::vector<fc::ShapeNode> nodes(n);
     for (int32_t u = 0; u < n; ++u) nodes[u] = fc::ShapeNode{node_area[u], node_ext ? node_ext[u] : 0};
     if (int rc = fc_run_sync(r)) return rc;  // a reader of the previous tables may still run
@@ -879,9 +888,9 @@ int fc_run_sample_plans(fc_run *r, int32_t c0, int32_t nc, int32_t n_times, cons
     const size_t want = plans ? cn * nt * npad : 0;
     const size_t held = want + (plans && npad != (size_t)n ? cn * nt * (size_t)n : 0);
     if (held > r->d_pl_rows.capacity()) {
-        size_t free_b = 0, total_b = 0;
-        HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-        if (want > free_b / 10)
+        bool fits = false;
+        if ((q = fits_free_tenth(want, fits))) return q;
+        if (!fits)
             return fail(FC_ERR_ARG, "fc_run_sample_plans: " + std::to_string(want) + " bytes of staged plans (" +
                                         std::to_string(nc) + " chains x " + std::to_string(n_times) + " times x " +
                                         std::to_string(npad) + ") exceed a tenth of the free device memory; " +
@@ -893,36 +902,28 @@ int fc_run_sample_plans(fc_run *r, int32_t c0, int32_t nc, int32_t n_times, cons
         std::copy(r->g.pop.begin(), r->g.pop.begin() + n, pp.begin());
         if ((q = r->d_pl_pop.upload(pp))) return q;
     }
-    // times, then the chains' |cut| and |B| at the window start (open_window has left the run idle)
-    std::vector<int64_t> in(nt + 2 * cn);
-    std::copy(times, times + n_times, in.begin());
-    for (int32_t i = 0; i < nc; ++i) {
-        in[nt + i] = s.sc[i].ser_cut0;
-        in[nt + cn + i] = s.sc[i].ser_nb0;
-    }
-    if ((q = r->d_pl_in.grow(in.size()))) return q;
-    HIP_TRY(hipMemcpy(r->d_pl_in, in.data(), in.size() * 8, hipMemcpyHostToDevice));
+    // the times (open_window has left the run idle)
+    if ((q = r->d_pl_in.grow(nt))) return q;
+    HIP_TRY(hipMemcpy(r->d_pl_in, times, nt * 8, hipMemcpyHostToDevice));
     OutPack out;
     if ((q = out.reserve(r, {cn * nt, cn * nt, cn * nt, cn * nt * k}))) return q;
     fc::PlansParams pp{};
     pp.log = s.log;
     pp.n_times = n_times;
     pp.times = r->d_pl_in;
-    pp.cut0 = r->d_pl_in + nt;
-    pp.nb0 = r->d_pl_in + nt + cn;
+    pp.cut0 = s.cut0;
+    pp.nb0 = s.nb0;
     pp.node_pop = r->d_pl_pop;
     pp.plans = plans ? r->d_pl_rows.get() : nullptr;
     pp.cut = cut ? out.at(0) : nullptr;
     pp.nb = nb ? out.at(1) : nullptr;
     pp.dist0 = dist0 ? out.at(2) : nullptr;
     pp.pops = pops ? out.at(3) : nullptr;
-    for (hipEvent_t &ev : r->pl_ev)
-        if (!ev) HIP_TRY(hipEventCreate(&ev));
     r->pl_timed = false;
-    HIP_TRY(hipEventRecord(r->pl_ev[0], r->stream));
+    if ((q = r->pl_ev.mark(0, r->stream))) return q;
     const int e = fc::launch_plans(pp, r->stream);
     if (e) return fail(FC_ERR_HIP, std::string("plan samples: ") + hipGetErrorString((hipError_t)e));
-    HIP_TRY(hipEventRecord(r->pl_ev[1], r->stream));
+    if ((q = r->pl_ev.mark(1, r->stream))) return q;
     // the rows, packed to n bytes: one strided copy, pitch npad -> n, on the device, then one
     // contiguous copy to the host (as every other reader's: no pitched copy into pageable memory)
     if (plans) {
@@ -934,7 +935,7 @@ int fc_run_sample_plans(fc_run *r, int32_t c0, int32_t nc, int32_t n_times, cons
         }
         HIP_TRY(hipMemcpyAsync(plans, src, cn * nt * (size_t)n, hipMemcpyDeviceToHost, r->stream));
     }
-    HIP_TRY(hipEventRecord(r->pl_ev[2], r->stream));
+    if ((q = r->pl_ev.mark(2, r->stream))) return q;
     if (int rc = out.fetch(r, {cut, nb, dist0, pops})) return rc;
     r->pl_timed = true;
     r->pl_copied = plans != nullptr;
@@ -944,10 +945,11 @@ int fc_run_sample_plans(fc_run *r, int32_t c0, int32_t nc, int32_t n_times, cons
 int fc_run_sample_plans_ms(fc_run *r, float *kernel_ms, float *copy_ms) {
     if (!r) return fail(FC_ERR_ARG, "fc_run_sample_plans_ms: null run");
     if (!r->pl_timed) return fail(FC_ERR_ARG, "fc_run_sample_plans_ms: no fc_run_sample_plans call recorded");
-    if (kernel_ms) HIP_TRY(hipEventElapsedTime(kernel_ms, r->pl_ev[0], r->pl_ev[1]));
+    if (kernel_ms)
+        if (int rc = r->pl_ev.elapsed(0, 1, kernel_ms)) return rc;
     if (copy_ms) {
         *copy_ms = 0.f;
-        if (r->pl_copied) HIP_TRY(hipEventElapsedTime(copy_ms, r->pl_ev[1], r->pl_ev[2]));
+        if (r->pl_copied) return r->pl_ev.elapsed(1, 2, copy_ms);
     }
     return FC_OK;
 }
@@ -979,19 +981,19 @@ int fc_run_heat_series(fc_run *r, int32_t c0, int32_t nc, uint32_t flags, int64_
     int q;
     // the outputs are kept by the run; a larger call has to fit a tenth of the free device memory
     if (total > r->d_ser_out.capacity()) {
-        size_t free_b = 0, total_b = 0;
-        HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-        if (total * 8 > free_b / 10)
+        bool fits = false;
+        if ((q = fits_free_tenth(total * 8, fits))) return q;
+        if (!fits)
             return fail(FC_ERR_ARG, "fc_run_heat_series: " + std::to_string(total * 8) + " bytes of outputs (" +
                                         std::to_string(nc) + " chains) exceed a tenth of the free device memory; " +
                                         "split the call by chains");
     }
     // the neighbour / edge rows and the device's LDS limit: once per run
     if (!r->ht_width) {
-        const int32_t W = fc::shapes_row_width(r->g.max_degree);
+        const int32_t W = fc::row_width(r->g.max_degree);
         if (W == 0) return fail(FC_ERR_UNSUPPORTED, "fc_run_heat_series: node degree above 16");
-        std::vector<fc::HeatSlot> rows;
-        fc::heat_build_rows(n, E, r->g.eu.data(), r->g.ev.data(), W, rows);
+        std::vector<fc::RowSlot> rows;
+        fc::build_rows(n, E, r->g.eu.data(), r->g.ev.data(), W, nullptr, -1, rows);
         if ((q = r->d_ht_rows.upload(rows))) return q;
         int dev = 0, optin = 0;
         if (hipGetDevice(&dev) != hipSuccess ||
@@ -1005,14 +1007,6 @@ int fc_run_heat_series(fc_run *r, int32_t c0, int32_t nc, uint32_t flags, int64_
     // workgroup per compute unit the LDS form measured slower)
     const int32_t form =
         (flags & FC_HEAT_LDS_ROWS) && image <= (size_t)r->ht_optin ? fc::kHeatFormLds : fc::kHeatFormGlobal;
-    // the chains' |cut| and |B| at the window start (open_window has left the run idle)
-    std::vector<int64_t> in(2 * cn);
-    for (int32_t i = 0; i < nc; ++i) {
-        in[i] = s.sc[i].ser_cut0;
-        in[cn + i] = s.sc[i].ser_nb0;
-    }
-    if ((q = r->d_ht_in.grow(in.size()))) return q;
-    HIP_TRY(hipMemcpy(r->d_ht_in, in.data(), in.size() * 8, hipMemcpyHostToDevice));
     OutPack out;
     if ((q = out.reserve(r, {len[0], len[1], len[2], len[3], len[4], len[5]}))) return q;
     fc::HeatParams hp{};
@@ -1021,21 +1015,19 @@ int fc_run_heat_series(fc_run *r, int32_t c0, int32_t nc, uint32_t flags, int64_
     hp.width = r->ht_width;
     hp.n_edges = E;
     hp.nb_width = nbw;
-    hp.cut0 = r->d_ht_in;
-    hp.nb0 = r->d_ht_in + cn;
+    hp.cut0 = s.cut0;
+    hp.nb0 = s.nb0;
     hp.cut_hist = cut_hist ? out.at(0) : nullptr;
     hp.nb_hist = nb_hist ? out.at(1) : nullptr;
     hp.cut_times = cut_times ? out.at(2) : nullptr;
     hp.moves = moves ? out.at(3) : nullptr;
     hp.last_move = last_move ? out.at(4) : nullptr;
     hp.dwell = dwell ? out.at(5) : nullptr;
-    for (hipEvent_t &ev : r->ht_ev)
-        if (!ev) HIP_TRY(hipEventCreate(&ev));
     r->ht_form = -1;
-    HIP_TRY(hipEventRecord(r->ht_ev[0], r->stream));
+    if ((q = r->ht_ev.mark(0, r->stream))) return q;
     const int e = fc::launch_heat(hp, form, r->stream);
     if (e) return fail(FC_ERR_HIP, std::string("heat-map series: ") + hipGetErrorString((hipError_t)e));
-    HIP_TRY(hipEventRecord(r->ht_ev[1], r->stream));
+    if ((q = r->ht_ev.mark(1, r->stream))) return q;
     if (int rc = out.fetch(r, {cut_hist, nb_hist, cut_times, moves, last_move, dwell})) return rc;
     r->ht_form = form;
     r->ht_lds = (int64_t)(form == fc::kHeatFormLds ? image : fc::heat_base_bytes(r->npad, r->ht_width));
@@ -1047,25 +1039,24 @@ int fc_run_heat_series_info(fc_run *r, int32_t *form, int64_t *lds_bytes, float 
     if (r->ht_form < 0) return fail(FC_ERR_ARG, "fc_run_heat_series_info: no fc_run_heat_series call recorded");
     if (form) *form = r->ht_form;
     if (lds_bytes) *lds_bytes = r->ht_lds;
-    if (kernel_ms) HIP_TRY(hipEventElapsedTime(kernel_ms, r->ht_ev[0], r->ht_ev[1]));
-    return FC_OK;
+    return kernel_ms ? r->ht_ev.elapsed(0, 1, kernel_ms) : FC_OK;
 }
 
 int fc_graph_heat_rows(const fc_graph *g, int32_t *width, int32_t *nbr, int32_t *eid) {
     if (!g || !width) return fail(FC_ERR_ARG, "fc_graph_heat_rows: null argument");
     fc_graph_info gi;
     if (int rc = fc_graph_get_info(g, &gi)) return rc;
-    const int32_t W = fc::shapes_row_width(gi.max_degree);
+    const int32_t W = fc::row_width(gi.max_degree);
     if (W == 0) return fail(FC_ERR_UNSUPPORTED, "fc_graph_heat_rows: node degree above 16");
     *width = W;
     if (!nbr && !eid) return FC_OK;
     std::vector<int32_t> eu((size_t)gi.n_edges + 1), ev((size_t)gi.n_edges + 1);
     if (int rc = fc_graph_edges(g, eu.data(), ev.data())) return rc;
-    std::vector<fc::HeatSlot> rows;
-    fc::heat_build_rows(gi.n_nodes, gi.n_edges, eu.data(), ev.data(), W, rows);
+    std::vector<fc::RowSlot> rows;
+    fc::build_rows(gi.n_nodes, gi.n_edges, eu.data(), ev.data(), W, nullptr, -1, rows);
     for (size_t i = 0; i < rows.size(); ++i) {
         if (nbr) nbr[i] = rows[i].nbr;
-        if (eid) eid[i] = rows[i].eid;
+        if (eid) eid[i] = rows[i].val;
     }
     return FC_OK;
 }

@@ -87,6 +87,27 @@ private:
     size_t cap_ = 0;
 };
 
+// N HIP events recorded along the last call of an entry point, for its elapsed-time read-out:
+// each created by its first mark(), destroyed with their holder (an fc_run: never copied).
+template <int N>
+struct EventMarks {
+    hipEvent_t ev[N] = {};
+
+    ~EventMarks() {
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+    int mark(int i, hipStream_t stream) {
+        if (!ev[i]) HIP_TRY(hipEventCreate(&ev[i]));
+        HIP_TRY(hipEventRecord(ev[i], stream));
+        return FC_OK;
+    }
+    int elapsed(int i, int j, float *ms) const {  // milliseconds from event i to event j
+        HIP_TRY(hipEventElapsedTime(ms, ev[i], ev[j]));
+        return FC_OK;
+    }
+};
+
 constexpr size_t kMaxLaunchEvents = 4096;  // per-launch HIP event pairs kept (fc_run_timings)
 
 }  // namespace fc
@@ -143,7 +164,8 @@ struct fc_run : fc::RunShape {
     // The series calls (fc_readout.cpp open_window / OutPack) share two buffers, grown on demand.
     // Every call fills what it reads of them and synchronises before it returns, so nothing is
     // carried from one call to the next
-    DevBuf<int64_t> d_ser_meta;  // per call: ev_len, t0, t_end of the chains read, [nc] each (LogWindow)
+    DevBuf<int64_t> d_ser_meta;  // per call: ev_len, t0, t_end (LogWindow), then |cut| and |B| at the window
+                                 // start, of the chains read, [nc] each
     DevBuf<int64_t> d_ser_out;   // per call: the int64 outputs of the election / compactness series,
                                  // one after the other
     DevBuf<double> d_fs_out;   // fc_run_frame_series output (slope, angle), grown on demand
@@ -170,7 +192,7 @@ struct fc_run : fc::RunShape {
     DevBuf<int8_t> d_el_cur;      // per call: current-assignment rows when they are not kept in LDS
     // compactness series (fc_run_set_shapes; fc_shapes.h, fc_shapes.hip).  sh_width 0: not set
     int32_t sh_width = 0, sh_n_edges = 0;
-    DevBuf<fc::ShapeSlot> d_sh_rows;   // [n * sh_width] neighbour rows
+    DevBuf<fc::RowSlot> d_sh_rows;     // [n * sh_width] neighbour rows
     DevBuf<fc::ShapeNode> d_sh_nodes;  // [n]
     DevBuf<int64_t> d_sh_edges;   // [sh_n_edges]
     // locality-splits series (fc_run_set_localities; fc_splits.h, fc_splits.hip).  sp_n_loc 0: not set
@@ -178,17 +200,16 @@ struct fc_run : fc::RunShape {
     DevBuf<int32_t> d_sp_loc;     // [n] node labels
     // plan samples (fc_run_sample_plans; fc_plans.h, fc_plans.hip): no setter, nothing kept but buffers
     DevBuf<int8_t> d_pl_rows;     // per call: the staged plan rows, npad bytes each, grown on demand
-    DevBuf<int64_t> d_pl_in;      // per call: times [n_times], then series_cut0 and series_nb0 [nc] each
+    DevBuf<int64_t> d_pl_in;      // per call: times [n_times]
     DevBuf<int32_t> d_pl_pop;     // [npad] node populations, 0 beyond n (uploaded by the first call with pops)
-    hipEvent_t pl_ev[3] = {nullptr, nullptr, nullptr};  // last call: before the kernel, after it, after the row copy
+    fc::EventMarks<3> pl_ev;      // last call: before the kernel, after it, after the row copy
     bool pl_timed = false, pl_copied = false;           // (fc_run_sample_plans_ms)
     // heat-map series (fc_run_heat_series; fc_heat.h, fc_heat.hip): no setter; the neighbour / edge rows
     // are built and uploaded by the first call and kept, like the frame tables.  ht_width 0: not yet
     int32_t ht_width = 0;
     int32_t ht_optin = 0;         // the device's opt-in dynamic LDS limit, queried by the first call
-    DevBuf<fc::HeatSlot> d_ht_rows;  // [n * ht_width]
-    DevBuf<int64_t> d_ht_in;      // per call: series_cut0 and series_nb0 [nc] each
-    hipEvent_t ht_ev[2] = {nullptr, nullptr};  // last call: before the kernel, after it
+    DevBuf<fc::RowSlot> d_ht_rows;   // [n * ht_width]
+    fc::EventMarks<2> ht_ev;      // last call: before the kernel, after it
     int32_t ht_form = -1;         // last call that launched: fc::kHeatFormLds / kHeatFormGlobal (-1: none yet)
     int64_t ht_lds = 0;           // ... and the dynamic LDS bytes of its workgroups
     char kname[96] = {0};       // last launched flip-kernel instance
@@ -209,10 +230,6 @@ struct fc_run : fc::RunShape {
     // The caller selects the run's device first (fc_run_destroy); the buffers free themselves.
     ~fc_run() {
         for (auto &pr : launch_events) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
-        for (hipEvent_t e : pl_ev)
-            if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : ht_ev)
-            if (e) (void)hipEventDestroy(e);
         if (stream) (void)hipStreamDestroy(stream);
     }
 

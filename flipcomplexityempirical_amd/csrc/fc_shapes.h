@@ -25,11 +25,7 @@ FC_HD int64_t shape_score(int64_t area, int64_t perim) {
     return q > (uint64_t)kShapeScoreMax ? kShapeScoreMax : (int64_t)q;
 }
 
-// A slot of a node's neighbour row: the neighbour's id (-1: empty, len 0) and the length shared
-struct alignas(8) ShapeSlot {
-    int32_t nbr, len;
-};
-// A node's own values
+// A node's own values (its neighbour rows are RowSlots of the length shared, 0 in an empty slot)
 struct alignas(8) ShapeNode {
     int32_t area, ext;
 };
@@ -37,7 +33,7 @@ struct alignas(8) ShapeNode {
 // Kernel parameters (passed by value).  Output rows are per chain of the call, [nc] rows each.
 struct ShapesParams {
     LogWindow log;            // the chains read and their window (fc_replay.h)
-    const ShapeSlot *rows;    // [n * width] neighbour rows
+    const RowSlot *rows;      // [n * width] neighbour rows
     const ShapeNode *nodes;   // [n]
     int32_t width;            // slots per row: 8 or 16
     int32_t n_edges;
@@ -48,9 +44,6 @@ struct ShapesParams {
     int64_t *pp_min_hist;     // [nc * (n_edges + 1)]
 };
 
-// Slots per neighbour row for a graph of this maximum degree (the kernel's instances), 0: none
-inline int32_t shapes_row_width(int32_t max_degree) { return max_degree <= 8 ? 8 : max_degree <= 16 ? 16 : 0; }
-
 // LDS bytes of the kernel's histograms: (k + 1) rows, the last one Qmin's (padded to 16 bytes)
 FC_HD size_t shapes_hist_bytes(int32_t k, int32_t n_edges) {
     return (8 * (size_t)(k + 1) * (size_t)(n_edges + 1) + 15) & ~(size_t)15;
@@ -58,7 +51,7 @@ FC_HD size_t shapes_hist_bytes(int32_t k, int32_t n_edges) {
 // LDS bytes of the kernel: the histograms, the initial area / perimeter table [2][32], the
 // chunk's neighbour rows and the current assignment
 inline size_t shapes_lds_bytes(int32_t npad, int32_t k, int32_t n_edges, int32_t width) {
-    return shapes_hist_bytes(k, n_edges) + 4 * 2 * 32 + sizeof(ShapeSlot) * 64 * (size_t)width +
+    return shapes_hist_bytes(k, n_edges) + 4 * 2 * 32 + sizeof(RowSlot) * 64 * (size_t)width +
            (((size_t)npad + 15) & ~(size_t)15);
 }
 // Whether a chain's image fits the default dynamic LDS limit

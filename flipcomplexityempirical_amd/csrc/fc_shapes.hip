@@ -19,41 +19,16 @@
 // in LDS before the next event reads it.
 #include <hip/hip_runtime.h>
 
-#include "fc_device.h"
+#include "fc_replay_dev.h"
 #include "fc_shapes.h"
 
 namespace fc {
 namespace {
 
+using dev::min_lanes32;
 using dev::rl32;
 using dev::rl64;
-
-// x of the lane a DPP control pairs this one with (every lane has a partner under these controls)
-template <int CTRL>
-__device__ __forceinline__ int32_t dpp(int32_t x) {
-    return __builtin_amdgcn_update_dpp(x, x, CTRL, 0xf, 0xf, false);
-}
-constexpr int kQuadSwap1 = 0xB1;     // quad_perm [1, 0, 3, 2]
-constexpr int kQuadSwap2 = 0x4E;     // quad_perm [2, 3, 0, 1]
-constexpr int kRowHalfMirror = 0x141;
-constexpr int kRowMirror = 0x140;
-
-// the sum of x over lanes 0 .. 15 (wave-uniform)
-__device__ __forceinline__ int32_t row0_sum(int32_t x) {
-    x += dpp<kQuadSwap1>(x);
-    x += dpp<kQuadSwap2>(x);
-    x += dpp<kRowHalfMirror>(x);
-    x += dpp<kRowMirror>(x);
-    return rl32(x, 0);
-}
-// the minimum of x over lanes 0 .. 31 (wave-uniform)
-__device__ __forceinline__ int32_t min_lanes32(int32_t x) {
-    x = min(x, dpp<kQuadSwap1>(x));
-    x = min(x, dpp<kQuadSwap2>(x));
-    x = min(x, dpp<kRowHalfMirror>(x));
-    x = min(x, dpp<kRowMirror>(x));
-    return min(rl32(x, 0), rl32(x, 16));
-}
+using dev::row0_sum;
 
 // searchsorted(edges, q, side="right"): the edges at or below q, lane l holding edge l
 // (INT64_MAX past the end)
@@ -63,7 +38,8 @@ __device__ __forceinline__ int32_t score_bin(int64_t eq, int32_t q) { return __p
 template <int W>
 __global__ __launch_bounds__(64) void shapes_kernel(const ShapesParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int RV = W / 2;  // 16-byte pieces of a row
+    using NbrRows = replay::Rows<W>;
+    constexpr int RV = NbrRows::RV;  // 16-byte pieces of a row
     const int lane = (int)threadIdx.x;
     const int32_t cl = (int32_t)blockIdx.x;
     const LogWindow &w = p.log;
@@ -73,7 +49,6 @@ __global__ __launch_bounds__(64) void shapes_kernel(const ShapesParams p) {
     int64_t *hist = (int64_t *)smem;                                   // [k + 1][nb], the last row Qmin's
     int32_t *tab = (int32_t *)(smem + shapes_hist_bytes(k, n_edges));  // [2][32] initial areas, perimeters
     int4 *stage4 = (int4 *)(tab + 64);                                 // [64][W] the chunk's neighbour rows
-    const ShapeSlot *stage = (const ShapeSlot *)stage4;
     int8_t *cur = (int8_t *)(stage4 + 64 * RV);                        // [npad]
 
     for (int i = lane; i < (k + 1) * nb; i += 64) hist[i] = 0;
@@ -118,51 +93,32 @@ __global__ __launch_bounds__(64) void shapes_kernel(const ShapesParams p) {
         mbin = score_bin(eq, qmin);
     }
 
-    const ulonglong2 *ev = (const ulonglong2 *)(w.events + (size_t)c * w.ev_cap);
-    const int64_t ne = w.ev_len[cl] < w.ev_cap ? w.ev_len[cl] : w.ev_cap;
-    // this lane's event of log index idx: its node (-1: none) and target
-    auto decode = [&](const ulonglong2 &e, int64_t idx, int &v, int &tg) {
-        v = (int)(e.y & 0xffffu);
-        tg = (int)((e.y >> 48) & 0xffu);
-        if (!(idx < ne && v < n && tg < k)) {
-            v = -1;
-            tg = 0;
-        }
-    };
+    const replay::Log log(w, cl);
+    const int64_t ne = log.ne;
+    // the next chunk's node values and rows (empty slots: length 0)
     auto load_row = [&](int v, int4 (&r)[RV], ShapeNode &nd) {
         nd = ShapeNode{0, 0};
-#pragma unroll
-        for (int q = 0; q < RV; ++q) r[q] = make_int4(-1, 0, -1, 0);
-        if (v >= 0) {
-            nd = p.nodes[v];
-            const int4 *row = (const int4 *)(p.rows + (size_t)v * W);
-#pragma unroll
-            for (int q = 0; q < RV; ++q) r[q] = row[q];
-        }
+        NbrRows::load(p.rows, v, 0, r);
+        if (v >= 0) nd = p.nodes[v];
     };
     // the events of the next chunk and of the one after it, and the next chunk's rows
-    ulonglong2 e1 = {0ull, 0ull}, e2 = {0ull, 0ull};
-    if (lane < ne) e1 = ev[lane];
-    if (64 + lane < ne) e2 = ev[64 + lane];
+    replay::Prefetch<2> nx(log, lane);
     int v1, tg1;
-    decode(e1, lane, v1, tg1);
+    replay::decode(nx.e[0], lane < ne, n, k, v1, tg1);
     int4 r1[RV];
     ShapeNode nd1;
     load_row(v1, r1, nd1);
     for (int64_t base = 0; base < ne; base += 64) {
-        const int64_t t = (int64_t)e1.x;
+        const int64_t t = replay::ev_t(nx.e[0]);
         const int v = v1, tg = tg1;
         const int32_t area = nd1.area, ext = nd1.ext;
-#pragma unroll
-        for (int q = 0; q < RV; ++q) stage4[lane * RV + q] = r1[q];
-        e1 = e2;
-        decode(e1, base + 64 + lane, v1, tg1);
+        NbrRows::stage(stage4, lane, r1);
+        replay::decode(nx.e[1], base + 64 + lane < ne, n, k, v1, tg1);
         load_row(v1, r1, nd1);
-        e2 = ulonglong2{0ull, 0ull};
-        if (base + 128 + lane < ne) e2 = ev[base + 128 + lane];
+        nx.advance(log, base, lane);
         __syncthreads();
 
-        const int cnt = (int)(ne - base < 64 ? ne - base : 64);
+        const int cnt = log.count(base);
         for (int i = 0; i < cnt; ++i) {
             const int vi = rl32(v, i);
             if (vi < 0) continue;
@@ -171,14 +127,13 @@ __global__ __launch_bounds__(64) void shapes_kernel(const ShapesParams p) {
             const int32_t ar = rl32(area, i), ex = rl32(ext, i);
             // slot `lane` of the node's row: the neighbour's district now, and the shared length
             // (the row and cur[v] are read together: one LDS latency, then the neighbours')
-            ShapeSlot s = ShapeSlot{-1, 0};
-            if (lane < W) s = stage[i * W + lane];
+            const RowSlot s = NbrRows::slot(stage4, i, lane, 0);
             const int cv = (int)cur[vi];
             const int dw = s.nbr >= 0 ? (int)cur[s.nbr] : -1;
             const int od = __builtin_amdgcn_readfirstlane(cv);
-            const int32_t l_all = row0_sum(s.len);
-            const int32_t l_old = row0_sum(dw == od ? s.len : 0);
-            const int32_t l_tgt = row0_sum(dw == td ? s.len : 0);
+            const int32_t l_all = row0_sum(s.val);
+            const int32_t l_old = row0_sum(dw == od ? s.val : 0);
+            const int32_t l_tgt = row0_sum(dw == td ? s.val : 0);
             if (od != td) {
                 if (lane == od || lane == td) {
                     const int64_t dt = te - t_last;

@@ -29,7 +29,7 @@
 // The chunk is then applied to the table, parts and cur by LDS adds.
 #include <hip/hip_runtime.h>
 
-#include "fc_device.h"
+#include "fc_replay_dev.h"
 #include "fc_splits.h"
 
 namespace fc {
@@ -37,24 +37,12 @@ namespace {
 
 using dev::rl32;
 using dev::rl64;
+using replay::bits_for;
+using replay::match_mask;
 
 __device__ __forceinline__ void lds_add64(int64_t *p, int64_t x) {
     atomicAdd((unsigned long long *)p, (unsigned long long)x);
 }
-
-// The lanes of `on` whose key `theirs` equals this lane's key `mine` (both below 2^bits, bits
-// wave-uniform): per key bit one ballot of the lanes that have it set, of which a lane keeps those
-// that agree with its own bit.  Call with the whole wave active.
-__device__ __forceinline__ uint64_t match_mask(uint32_t mine, uint32_t theirs, int bits, uint64_t on) {
-    uint64_t differ = 0;
-    for (int b = 0; b < bits; ++b) {
-        const uint64_t has = __ballot((theirs >> b) & 1u);
-        differ |= ((mine >> b) & 1u) ? ~has : has;
-    }
-    return ~differ & on;
-}
-// bits that hold every value below x (x >= 1)
-__device__ __forceinline__ int bits_for(int32_t x) { return x <= 1 ? 0 : 32 - __builtin_clz((uint32_t)(x - 1)); }
 
 __global__ __launch_bounds__(64) void splits_kernel(const SplitsParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -117,29 +105,25 @@ __global__ __launch_bounds__(64) void splits_kernel(const SplitsParams p) {
     int32_t splits = (int32_t)s0, excess = (int32_t)x0;  // wave-uniform: after the last event replayed
     int64_t sq_acc = 0;                                   // this lane's share of sum_t (sq_t - sq_t0)
 
-    const ulonglong2 *ev = (const ulonglong2 *)(w.events + (size_t)ch * w.ev_cap);
-    const int64_t ne = w.ev_len[cl] < w.ev_cap ? w.ev_len[cl] : w.ev_cap;
-    // this lane's event of the next chunk, loaded one chunk ahead
-    ulonglong2 nx = {0ull, 0ull};
-    if (lane < ne) nx = ev[lane];
+    const replay::Log log(w, cl);
+    const int64_t ne = log.ne;
+    replay::Prefetch<1> nx(log, lane);  // this lane's event of the next chunk, loaded one chunk ahead
     // the yields before the first event
     if (lane == 0) {
-        const int64_t head = (ne > 0 ? (int64_t)nx.x : t1) - t0;
+        const int64_t head = (ne > 0 ? replay::ev_t(nx.e[0]) : t1) - t0;
         hs[min(max(splits, 0), L)] += head;
         he[min(max(excess, 0), X)] += head;
     }
     __syncthreads();
 
     for (int64_t base = 0; base < ne; base += 64) {
-        const int64_t t = (int64_t)nx.x;
-        int tg = (int)((nx.y >> 48) & 0xffu);
-        int v = (int)(nx.y & 0xffffu);
-        const bool valid = base + lane < ne && v < n && tg < k;
-        if (!valid) { v = -1; tg = 0; }
-        if (base + 64 + lane < ne) nx = ev[base + 64 + lane];
-        const int cnt = (int)(ne - base < 64 ? ne - base : 64);
+        const int64_t t = replay::ev_t(nx.e[0]);
+        int v, tg;
+        const bool valid = replay::decode(nx.e[0], base + lane < ne, n, k, v, tg);
+        nx.advance(log, base, lane);
+        const int cnt = log.count(base);
         // the first yield after this chunk's last run
-        const int64_t t_next = base + 64 < ne ? rl64((int64_t)nx.x, 0) : t1;
+        const int64_t t_next = base + 64 < ne ? rl64(replay::ev_t(nx.e[0]), 0) : t1;
         const int32_t loc = valid ? p.node_loc[v] : 0;
         // 1. the node's district before the event: the target of the latest earlier lane with the
         // same node, else cur[v]

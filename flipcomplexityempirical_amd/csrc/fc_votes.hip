@@ -15,7 +15,7 @@
 // value * (t - t_since) when it changes, and once more at the window's end.
 #include <hip/hip_runtime.h>
 
-#include "fc_device.h"
+#include "fc_replay_dev.h"
 #include "fc_votes.h"
 
 namespace fc {
@@ -121,18 +121,20 @@ __global__ __launch_bounds__(64) void votes_kernel(const VotesParams p) {
         }
     }
 
-    const ulonglong2 *ev = (const ulonglong2 *)(w.events + (size_t)c * w.ev_cap);
-    const int64_t ne = w.ev_len[cl] < w.ev_cap ? w.ev_len[cl] : w.ev_cap;
-    // this lane's event of the next chunk, loaded one chunk ahead
-    ulonglong2 nx = {0ull, 0ull};
-    if (lane < ne) nx = ev[lane];
+    const replay::Log log(w, cl);
+    const int64_t ne = log.ne;
+    // this lane's event of the next chunk, loaded one chunk ahead.  (replay::Prefetch<1> and
+    // replay::decode, spelt here: behind the calls the compiler no longer carries `valid` into the
+    // loads below, and most instances' code, a dozen's registers, move)
+    replay::Event nx = {0ull, 0ull};
+    if (lane < ne) nx = log.ev[lane];
     for (int64_t base = 0; base < ne; base += 64) {
-        const int64_t t = (int64_t)nx.x;
-        int tg = (int)((nx.y >> 48) & 0xffu);
-        int v = (int)(nx.y & 0xffffu);
+        const int64_t t = replay::ev_t(nx);
+        int tg = replay::ev_target(nx);
+        int v = replay::ev_node(nx);
         const bool valid = base + lane < ne && v < n && tg < k;
         if (!valid) { v = -1; tg = 0; }
-        if (base + 64 + lane < ne) nx = ev[base + 64 + lane];
+        if (base + 64 + lane < ne) nx = log.ev[base + 64 + lane];
         // the node's column row, and per election its two columns (a memory index, not a register one)
         int32_t cr[NC], cra[NE], crb[NE];
 #pragma unroll
@@ -144,7 +146,7 @@ __global__ __launch_bounds__(64) void votes_kernel(const VotesParams p) {
         }
         int old = valid ? cur_get(v) : 0;
         bool last = true;
-        const int cnt = (int)(ne - base < 64 ? ne - base : 64);
+        const int cnt = log.count(base);
         for (int j = 0; j < cnt; ++j) {
             const int vj = rl32(v, j), tj = rl32(tg, j);
             if (vj == v) {

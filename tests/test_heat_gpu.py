@@ -158,7 +158,7 @@ def test_chunk_edges_and_windows(gpu, cref):
     fs = flip_setup(name)
     spec = fs["spec"]
     run = _flip_run(name, 1501, diag=FUSED | _lib.FC_DIAG_WAIT)  # (the oracle draws the waits too)
-    for want in (0, 1, 63, 64, 65):
+    for want in (0, 1, 63, 64, 65, 127, 128, 129):  # (from 128 on the second chunk read ahead is refilled)
         for _ in range(200):  # one step per launch: the count grows by at most one
             if int(run.stats()["events"][0]) == want:
                 break

@@ -105,13 +105,16 @@ def test_grid_k2_neighbours_inside_a_chunk(gpu, weights):
 
 def test_chunk_boundaries_and_windows(gpu):
     """Reads at event counts around the chunk size: every chain at 0 events, some chain at 0 while
-    others have some, some chain at exactly 64 and at 65; then a window reset mid-run, read whole
-    and as a sub-range of chains."""
+    others have some, some chain at exactly 64 and at 65, and at 127, 128 and 129 (two chunks and
+    the refill of the second one read ahead); then a window reset mid-run, read whole and as a
+    sub-range of chains."""
     spec, run, inits = _grid_run(4000)
     shapes = _random_shapes(spec)
     ms = _check(run, shapes, inits)  # before the first launch: one yield, no event
     assert all(m["yields"] == 1 for m in ms)
     want = {"zero": lambda e: e.min() == 0 < e.max(), "full": lambda e: (e == 64).any(), "over": lambda e: (e == 65).any()}
+    # a second chunk read ahead that is refilled: the chain at base 1.0 logs an event per step
+    want.update({f"at {m}": (lambda e, m=m: (e == m).any()) for m in (127, 128, 129)})
     for _ in range(1500):  # one step per launch: a chain's count grows by at most one
         run.steps(1)
         e = run.stats()["events"]

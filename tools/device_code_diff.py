@@ -3,7 +3,10 @@
 Extracts the gfx950 code objects of two builds of libflipchain.so (the .hip_fatbin section's
 uncompressed offload bundles) and compares, by symbol name, the bytes of every function and of
 every kernel descriptor (*.kd) of the first build with the second's.  Needs no GPU.  Prints the
-counts and every symbol that is missing or differs (DESIGN.md §5h records a run)."""
+counts and every symbol that is missing or differs (DESIGN.md §5h records a run); for a function
+that differs, both sizes and whether the two disassemblies hold the same instructions, counted by
+mnemonic (so: the same code in another order or other registers)."""
+import collections
 import hashlib
 import os
 import re
@@ -59,17 +62,31 @@ def symbols(lib):
                 continue
             _, saddr, soff = secs[ndx]
             body = blob[soff + addr - saddr: soff + addr - saddr + size]
-            syms[name] = hashlib.sha256(body).hexdigest()
+            syms[name] = (hashlib.sha256(body).hexdigest(), size, path)
     return syms
+
+
+def mnemonics(sym, name):
+    """The function's instructions, counted by mnemonic."""
+    out = subprocess.run([LLVM + "llvm-objdump", "-d", "--disassemble-symbols=" + name, sym[2]],
+                         capture_output=True, text=True, check=True).stdout
+    return collections.Counter(m.group(1) for m in re.finditer(r"^\s+([a-z]\w*)\b.*//", out, re.M))
 
 
 a, b = symbols(sys.argv[1]), symbols(sys.argv[2])
 missing = [s for s in a if s not in b]
-differ = [s for s in a if s in b and a[s] != b[s]]
+differ = [s for s in a if s in b and a[s][0] != b[s][0]]
 new = [s for s in b if s not in a]
 print(f"parent symbols {len(a)} (functions {sum(1 for s in a if not s.endswith('.kd'))}, descriptors {sum(1 for s in a if s.endswith('.kd'))}); "
       f"identical {len(a) - len(missing) - len(differ)}; missing {len(missing)}; differ {len(differ)}; new in this build {len(new)}")
-for s in missing + differ:
+for s in missing:
     print("  MOVED", s)
+for s in differ:
+    if s.endswith(".kd"):
+        print("  MOVED", s)
+        continue
+    ma, mb = mnemonics(a[s], s), mnemonics(b[s], s)
+    print(f"  MOVED {s}: bytes {a[s][1]} -> {b[s][1]}; instructions {sum(ma.values())} -> {sum(mb.values())}, "
+          f"mnemonic multiset {'same' if ma == mb else 'differs'}")
 for s in new:
     print("  new", s)
