@@ -38,6 +38,7 @@ FC_CON_CONTIG, FC_CON_POP, FC_CON_BOUNDARY, FC_CON_FIXED, FC_CON_EMPTY = 0x1, 0x
 
 EXPORTED = [
     "fc_graph_create", "fc_graph_get_info", "fc_graph_edges", "fc_graph_rings", "fc_graph_destroy",
+    "fc_seed_params_init", "fc_graph_seed_plans", "fc_seed_kernel_name",
     "fc_params_init", "fc_run_create", "fc_run_steps", "fc_run_set_tape", "fc_run_set_initial_wait", "fc_run_sync", "fc_run_last_ms", "fc_run_timings",
     "fc_run_read_stats", "fc_run_read_state", "fc_run_read_pops", "fc_run_read_trace", "fc_run_read_recom_trace",
     "fc_run_trace_reset", "fc_run_read_hist", "fc_run_checkpoint", "fc_run_restore",
@@ -89,6 +90,18 @@ class Params(ctypes.Structure):
                 ("chain_pop_bounds", _P(ctypes.c_int64)),
                 # k = 2 node stream: FC_STREAM_NODE / FC_STREAM_BAND
                 ("stream", ctypes.c_int32), ("tune_multi_flip", ctypes.c_int32)]
+
+
+class SeedParams(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("abi_version", ctypes.c_uint32), ("k", ctypes.c_int32),
+                ("pop_lo", ctypes.c_int64), ("pop_hi", ctypes.c_int64), ("seed", ctypes.c_uint64),
+                ("plan_id_offset", ctypes.c_uint32), ("device", ctypes.c_int32), ("node_repeats", ctypes.c_int32),
+                ("max_attempts", ctypes.c_int32), ("max_restarts", ctypes.c_int32)]
+
+
+class SeedStats(ctypes.Structure):
+    _fields_ = [("attempts", ctypes.c_int64), ("trees", ctypes.c_int64), ("restarts", ctypes.c_int32),
+                ("ok", ctypes.c_int32), ("cut", ctypes.c_int32), ("nb", ctypes.c_int32)]
 
 
 class ChainStats(ctypes.Structure):
@@ -198,6 +211,9 @@ def load(build_if_missing: bool = True, allow_variant: bool = False):
     L.fc_graph_rings.argtypes = [vp, _P(i32), _P(ctypes.c_uint64)]
     L.fc_graph_destroy.argtypes = [vp]
     L.fc_graph_destroy.restype = None
+    L.fc_seed_params_init.argtypes = [_P(SeedParams), u32]
+    L.fc_graph_seed_plans.argtypes = [vp, _P(SeedParams), i32, _P(ctypes.c_int8), _P(SeedStats), _P(ctypes.c_float)]
+    L.fc_seed_kernel_name.argtypes = [ctypes.c_char_p, i32]
     L.fc_params_init.argtypes = [_P(Params), u32]
     L.fc_run_create.argtypes = [vp, _P(Params), i32, _P(ctypes.c_int8), _P(dbl), _P(vp)]
     L.fc_run_steps.argtypes = [vp, i64, i64, vp]

@@ -446,6 +446,39 @@ def recom(partition, pop_col, pop_target, epsilon, node_repeats=1):
                 return partition.flip(flips)
 
 
+def recursive_tree_part(graph, parts, pop_target, pop_col, epsilon, node_repeats=1, *, seed: int = 0,
+                        plan_id: int = 0, device: int = 0) -> Dict[Hashable, Any]:
+    """gerrychain 0.2 ``recursive_tree_part`` [gc-0.2] on the device: a random plan ``{node: part}``
+    of ``len(parts)`` connected districts, cut off a shrinking remainder one at a time by
+    ``bipartition_tree`` (``FlipGraph.seed_plans``).  It is the start plan of a
+    ReCom or flip workflow: ``Partition(graph, recursive_tree_part(...), updaters)``.
+
+    The population rule is integer: a district's population ``s`` must satisfy
+    ``|s - pop_target| <= epsilon * pop_target``, as the inclusive integer bounds computed here
+    once.  This replaces 0.2's float test ``abs(s - pop_target) < epsilon * pop_target``, which it
+    applies to the piece that is cut off only.  Unlike 0.2, every district -- the last one, the
+    remainder, included -- is inside the bounds: a cut must also leave the remainder room for the
+    districts still to come.  The result is a function of the arguments (``seed`` and ``plan_id``
+    select the random stream); it raises ``RuntimeError`` when no plan is found."""
+    from .engine import FlipGraph
+    parts = list(parts)
+    for n in graph.nodes:
+        if pop_col not in graph.nodes[n]:
+            raise ValueError(f"node {n!r} has no attribute {pop_col!r}")
+    spec = from_networkx(graph, pop_attr=pop_col,
+                         pos={n: (graph.nodes[n]["pos"] if "pos" in graph.nodes[n] else n) for n in graph.nodes}
+                         if all(isinstance(n, tuple) and len(n) == 2 for n in graph.nodes) else None)
+    slack = float(epsilon) * float(pop_target)
+    lo, hi = int(math.ceil(float(pop_target) - slack)), int(math.floor(float(pop_target) + slack))
+    fg = FlipGraph(spec)
+    try:
+        plans, _ = fg.seed_plans(len(parts), 1, pop_bounds=(lo, hi), seed=seed, plan_id_offset=plan_id,
+                                 node_repeats=node_repeats, device=device)
+    finally:
+        fg.close()
+    return {nd: parts[int(d)] for nd, d in zip(spec.nodes, plans[0])}
+
+
 uniform_accept = UniformAccept()
 annealing_cut_accept_backwards = AnnealingCutAcceptBackwards()
 

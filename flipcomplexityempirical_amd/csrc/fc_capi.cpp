@@ -19,6 +19,7 @@ namespace {
 
 constexpr int kWaveSlots = 64;
 thread_local std::string g_err;
+thread_local char g_seed_kname[96] = {0};  // the calling thread's last launched seed-plan instance
 
 }  // namespace
 
@@ -126,6 +127,106 @@ int fc_graph_rings(const fc_graph *g, int32_t *ring, uint64_t *meta) {
 }
 
 void fc_graph_destroy(fc_graph *g) { delete g; }
+
+int fc_seed_params_init(fc_seed_params *p, uint32_t struct_size) {
+    if (!p) return fail(FC_ERR_ARG, "fc_seed_params_init: null argument");
+    if (struct_size != sizeof(fc_seed_params))
+        return fail(FC_ERR_ARG, "fc_seed_params_init: struct_size " + std::to_string(struct_size) +
+                                    " != sizeof(fc_seed_params) " + std::to_string(sizeof(fc_seed_params)) +
+                                    " (the caller's flipchain.h is another version)");
+    std::memset(p, 0, sizeof *p);
+    p->struct_size = (uint32_t)sizeof(fc_seed_params);
+    p->abi_version = FC_ABI_VERSION;
+    p->k = 2;
+    p->pop_lo = 0;
+    p->pop_hi = INT64_MAX;
+    return FC_OK;
+}
+
+int fc_graph_seed_plans(const fc_graph *gr, const fc_seed_params *p, int32_t n_plans, int8_t *assign_out,
+                        fc_seed_stats *stats_out, float *kernel_ms) {
+    if (!gr || !p) return fail(FC_ERR_ARG, "fc_graph_seed_plans: null argument");
+    // ---- host: checks, defaults, tables (fc_plan.cpp) -------------------------------------
+    const fc::HostGraph &g = gr->h;
+    fc::SeedPlan sp;
+    std::string err;
+    if (int rc = fc::plan_seed(g, *p, n_plans, sp, err)) return fail(rc, err);
+    if (kernel_ms) *kernel_ms = 0.0f;
+    if (n_plans == 0) return FC_OK;
+    if (!assign_out) return fail(FC_ERR_ARG, "fc_graph_seed_plans: null assign_out");
+    const size_t P = (size_t)n_plans, n = (size_t)g.n, E = (size_t)g.n_edges, npad = (size_t)sp.npad;
+
+    // ---- device ---------------------------------------------------------------------------
+    HIP_TRY(hipSetDevice(p->device));
+    bool fits = false;
+    const size_t want = P * (npad + sizeof(fc_seed_stats)) + sp.node_recs.size() + (sp.nbe.size() + sp.eslot.size()) * 4 +
+                        2 * std::max<size_t>(E, 1) * 4;
+    if (int rc = fits_free_tenth(want, fits)) return rc;
+    if (!fits)
+        return fail(FC_ERR_NOMEM, "fc_graph_seed_plans: " + std::to_string(n_plans) + " plan rows and the graph tables (" +
+                                      std::to_string(want) + " bytes) exceed a tenth of the free device memory; split the "
+                                      "call (plan_id_offset keeps the plans the same)");
+    DevBuf<unsigned char> d_graph;
+    DevBuf<uint32_t> d_nbe, d_eslot;
+    DevBuf<int32_t> d_eu, d_ev;
+    DevBuf<int8_t> d_assign;
+    DevBuf<fc_seed_stats> d_stats;
+    int rc;
+    if ((rc = d_graph.upload(sp.node_recs))) return rc;
+    if ((rc = d_nbe.upload(sp.nbe))) return rc;
+    if ((rc = d_eslot.upload(sp.eslot))) return rc;
+    // (one entry at least, so that an edgeless graph still hands the kernel a buffer)
+    if ((rc = d_eu.alloc_zero(std::max<size_t>(E, 1)))) return rc;
+    if ((rc = d_ev.alloc_zero(std::max<size_t>(E, 1)))) return rc;
+    if (E) {
+        HIP_TRY(hipMemcpy(d_eu, g.eu.data(), E * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_ev, g.ev.data(), E * 4, hipMemcpyHostToDevice));
+    }
+    if ((rc = d_assign.alloc(P * npad))) return rc;
+    if ((rc = d_stats.alloc(P))) return rc;
+    fc::SeedParams q{};
+    q.graph = d_graph;
+    q.nbe = d_nbe;
+    q.eslot = d_eslot;
+    q.eu = d_eu;
+    q.ev = d_ev;
+    q.nb_d = sp.nb_d;
+    q.n = g.n;
+    q.n_edges = g.n_edges;
+    q.n_plans = n_plans;
+    q.chain_lds_bytes = sp.chain_lds_bytes;
+    q.k = sp.p.k;
+    q.plan_id_offset = sp.p.plan_id_offset;
+    q.seed_lo = (uint32_t)sp.p.seed;
+    q.seed_hi = (uint32_t)(sp.p.seed >> 32);
+    q.pop_lo = sp.p.pop_lo;
+    q.pop_hi = sp.p.pop_hi;
+    q.pop_total = sp.pop_total;
+    q.node_repeats = sp.p.node_repeats;
+    q.max_attempts = sp.p.max_attempts;
+    q.max_restarts = sp.p.max_restarts;
+    q.assign = d_assign;
+    q.stats = d_stats;
+    fc::EventMarks<2> ev;
+    if (kernel_ms && (rc = ev.mark(0, nullptr))) return rc;
+    const int e = fc::launch_seed(q, g.ring_max, nullptr, g_seed_kname, sizeof g_seed_kname);
+    if (e != 0) return fail(FC_ERR_HIP, std::string("seed kernel launch: ") + hipGetErrorString((hipError_t)e));
+    if (kernel_ms && (rc = ev.mark(1, nullptr))) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    if (kernel_ms && (rc = ev.elapsed(0, 1, kernel_ms))) return rc;
+    // ---- copy back, the row padding stripped ------------------------------------------------
+    std::vector<int8_t> rows(P * npad);
+    HIP_TRY(hipMemcpy(rows.data(), d_assign, rows.size(), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < P; ++i) std::memcpy(assign_out + i * n, rows.data() + i * npad, n);
+    if (stats_out) HIP_TRY(hipMemcpy(stats_out, d_stats, P * sizeof(fc_seed_stats), hipMemcpyDeviceToHost));
+    return FC_OK;
+}
+
+int fc_seed_kernel_name(char *buf, int32_t cap) {
+    if (!buf || cap <= 0) return fail(FC_ERR_ARG, "fc_seed_kernel_name: null argument");
+    std::snprintf(buf, (size_t)cap, "%s", g_seed_kname);
+    return FC_OK;
+}
 
 int fc_params_init(fc_params *p, uint32_t struct_size) {
     if (!p) return fail(FC_ERR_ARG, "fc_params_init: null argument");

@@ -220,6 +220,23 @@ inline int recom_lds_bytes(int n, int ring_max) { return (ring_max == 8 ? 14 : 1
 int launch_recom(const RecomParams &p, fc_event *events, int64_t ev_cap, int ring_max, void *stream, char *name,
                  size_t name_cap);
 
+// Seed-plan kernel parameters (fc_seed.hip): the graph tables are the ReCom kernel's, the LDS
+// layout and workgroup shape too (recom_lds_bytes, waves_per_block); one wave per plan.
+struct SeedParams {
+    const void *graph;             // NodeRec<RMAX>[n]
+    const uint32_t *nbe;           // [n * nb_d] neighbour rows (RecomParams.nbe)
+    const uint32_t *eslot;         // [n_edges]
+    const int32_t *eu, *ev;        // [n_edges]
+    int32_t nb_d;
+    int32_t n, n_edges, n_plans, chain_lds_bytes, k;
+    uint32_t plan_id_offset, seed_lo, seed_hi;
+    int64_t pop_lo, pop_hi, pop_total;
+    int32_t node_repeats, max_attempts, max_restarts;  // resolved: all >= 1, >= 1, >= 0
+    int8_t *assign;                // [n_plans * npad] rows padded to a multiple of 16 nodes
+    fc_seed_stats *stats;          // [n_plans]
+};
+int launch_seed(const SeedParams &p, int ring_max, void *stream, char *name, size_t name_cap);
+
 // Launch wrappers.  Return a hipError_t as int.
 // `name` (may be null) receives the launched instance, spelled as rocprofv3 reports it.
 int launch_flipk(const KParams &p, int ring_max, void *stream, char *name, size_t name_cap);  // k > 2 (fc_kernels.hip)

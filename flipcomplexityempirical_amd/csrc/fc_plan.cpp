@@ -49,7 +49,7 @@ bool district_contiguous(const HostGraph &g, const int8_t *a, int k, std::vector
 
 // the device node records as bytes, the run's frozen nodes marked (FC_CON_FIXED)
 template <int RMAX>
-std::vector<unsigned char> pack_records(const HostGraph &g, const fc_params &p) {
+std::vector<unsigned char> pack_records(const HostGraph &g, const int32_t *frozen, int32_t n_frozen) {
     std::vector<NodeRec<RMAX>> recs(g.n);
     for (int32_t v = 0; v < g.n; ++v) {
         auto &r = recs[v];
@@ -62,7 +62,7 @@ std::vector<unsigned char> pack_records(const HostGraph &g, const fc_params &p) 
             r.ring[j >> 1] |= x << (16 * (j & 1));
         }
     }
-    for (int32_t i = 0; i < p.n_frozen; ++i) recs[p.frozen[i]].meta |= kMetaFrozen;
+    for (int32_t i = 0; i < n_frozen; ++i) recs[frozen[i]].meta |= kMetaFrozen;
     const unsigned char *b = (const unsigned char *)recs.data();
     return std::vector<unsigned char>(b, b + recs.size() * sizeof(NodeRec<RMAX>));
 }
@@ -478,30 +478,87 @@ uint64_t hash_params(const fc_params *p, const double *bases, const RunPlan &r) 
 }
 
 void recom_tables(const HostGraph &g, double base, RunPlan &r) {
-    const int32_t n = g.n, E = g.n_edges;
-    // the neighbours of each node in ring order with their edge ids (node ids and edge ids
-    // < 65535: n <= 8000, degree <= 16), and each edge end's index in the other end's row:
-    // the spanning-tree scan reads one row per node instead of its ring and ring edge ids
-    const int R = g.ring_max;
-    r.nb_d = std::max(4, (g.max_degree + 3) / 4 * 4);
-    r.nbe.assign((size_t)n * r.nb_d, ~0u);
-    r.eslot.assign((size_t)std::max(E, 1), 0u);
-    for (int32_t x = 0; x < n; ++x) {
-        int k = 0;
-        for (int j = 0; j < R; ++j) {
-            const int32_t e = g.ring_eid[(size_t)x * R + j];
-            if (e < 0) continue;
-            r.nbe[(size_t)x * r.nb_d + k] = (uint32_t)g.ring[(size_t)x * R + j] | ((uint32_t)e << 16);
-            r.eslot[e] |= (uint32_t)k << (g.eu[e] == x ? 0 : 8);
-            ++k;
-        }
-    }
+    const int32_t E = g.n_edges;
+    neighbour_rows(g, r.nb_d, r.nbe, r.eslot);
     // cut_accept: random() < base ** (cut - cut'), cut - cut' in [-E, E]
     r.recom_thresh.resize(2 * (size_t)E + 1);
     for (int32_t dd = -E; dd <= E; ++dd) r.recom_thresh[dd + E] = u53_threshold(std::pow(base, (double)dd));
 }
 
 }  // namespace
+
+void neighbour_rows(const HostGraph &g, int32_t &nb_d, std::vector<uint32_t> &nbe, std::vector<uint32_t> &eslot) {
+    const int32_t n = g.n, E = g.n_edges;
+    // the neighbours of each node in ring order with their edge ids (node ids and edge ids
+    // < 65535: n <= 8000, degree <= 16), and each edge end's index in the other end's row:
+    // the spanning-tree scan reads one row per node instead of its ring and ring edge ids
+    const int R = g.ring_max;
+    nb_d = std::max(4, (g.max_degree + 3) / 4 * 4);
+    nbe.assign((size_t)n * nb_d, ~0u);
+    eslot.assign((size_t)std::max(E, 1), 0u);
+    for (int32_t x = 0; x < n; ++x) {
+        int k = 0;
+        for (int j = 0; j < R; ++j) {
+            const int32_t e = g.ring_eid[(size_t)x * R + j];
+            if (e < 0) continue;
+            nbe[(size_t)x * nb_d + k] = (uint32_t)g.ring[(size_t)x * R + j] | ((uint32_t)e << 16);
+            eslot[e] |= (uint32_t)k << (g.eu[e] == x ? 0 : 8);
+            ++k;
+        }
+    }
+}
+
+int plan_seed(const HostGraph &g, const fc_seed_params &p, int32_t n_plans, SeedPlan &s, std::string &err) {
+    const std::string w = "fc_graph_seed_plans: ";
+    if (p.struct_size != sizeof(fc_seed_params) || p.abi_version != FC_ABI_VERSION)
+        return bad(err, FC_ERR_ARG, w + "fc_seed_params.struct_size " + std::to_string(p.struct_size) + " / abi_version " +
+                                    std::to_string(p.abi_version) + " do not match this library (" +
+                                    std::to_string(sizeof(fc_seed_params)) + " / " + std::to_string(FC_ABI_VERSION) +
+                                    "): set them with fc_seed_params_init");
+    if (n_plans < 0) return bad(err, FC_ERR_ARG, w + "n_plans must be >= 0");
+    if (p.k < 2 || p.k > kMaxKGeneral) return bad(err, FC_ERR_ARG, w + "k must be in [2, 32]");
+    if (p.pop_lo > p.pop_hi)
+        return bad(err, FC_ERR_ARG, w + "pop_lo " + std::to_string(p.pop_lo) + " > pop_hi " + std::to_string(p.pop_hi));
+    if (p.node_repeats < 0 || p.max_attempts < 0 || p.max_restarts < 0)
+        return bad(err, FC_ERR_ARG, w + "node_repeats, max_attempts and max_restarts must be >= 0 (0: the default)");
+    if (p.max_restarts >= (1 << 24))  // the attempt is bits 8..31 of the draw index
+        return bad(err, FC_ERR_ARG, w + "max_restarts must be below 2^24");
+    if (g.n > 8000)
+        return bad(err, FC_ERR_UNSUPPORTED, w + "seed plans keep a plan's spanning tree in LDS (n <= 8000)");
+    int64_t total = 0;
+    for (int32_t u = 0; u < g.n; ++u) {
+        if (g.pop[u] < 0) return bad(err, FC_ERR_UNSUPPORTED, w + "node populations must be >= 0");
+        total += g.pop[u];
+    }
+    // fc_seed.hip sums subtree populations in int32 and marks the subset in bit 31, as fc_recom.hip does
+    if (total > INT32_MAX)
+        return bad(err, FC_ERR_UNSUPPORTED, w + "seed plans sum subtree populations in 31 bits (population total " +
+                                            std::to_string(total) + " exceeds INT32_MAX = 2147483647)");
+    if (g.max_degree > 16) return bad(err, FC_ERR_UNSUPPORTED, w + "node degree above 16");
+    if (!g.connected) return bad(err, FC_ERR_UNSUPPORTED, w + "the graph must be connected");
+    // k districts inside [lo, hi] must be able to hold the total (bounds beyond the total are
+    // clipped first, so that the products stay in int64)
+    const int64_t lo = std::max<int64_t>(p.pop_lo, -1), hi = std::min<int64_t>(p.pop_hi, total);
+    if (lo > total || (int64_t)p.k * lo > total)
+        return bad(err, FC_ERR_ARG, w + "k * pop_lo = " + std::to_string(p.k) + " * " + std::to_string(p.pop_lo) +
+                                    " exceeds the population total " + std::to_string(total));
+    if (hi < 0 || (int64_t)p.k * hi < total)
+        return bad(err, FC_ERR_ARG, w + "k * pop_hi = " + std::to_string(p.k) + " * " + std::to_string(p.pop_hi) +
+                                    " is below the population total " + std::to_string(total));
+    s.p = p;
+    // (a bound outside [0, total] admits what the clipped one admits: populations are in [0, total])
+    s.p.pop_lo = std::max<int64_t>(p.pop_lo, 0);
+    s.p.pop_hi = hi;
+    s.p.node_repeats = p.node_repeats > 0 ? p.node_repeats : 1;
+    s.p.max_attempts = p.max_attempts > 0 ? p.max_attempts : 256;
+    s.p.max_restarts = p.max_restarts > 0 ? p.max_restarts : 16;
+    s.pop_total = total;
+    s.npad = (g.n + 15) & ~15;
+    s.chain_lds_bytes = (recom_lds_bytes(g.n, g.ring_max) + 15) & ~15;
+    s.node_recs = g.ring_max == 8 ? pack_records<8>(g, nullptr, 0) : pack_records<16>(g, nullptr, 0);
+    neighbour_rows(g, s.nb_d, s.nbe, s.eslot);
+    return FC_OK;
+}
 
 int plan_run(const HostGraph &g, const fc_params &params, int32_t n_chains, const int8_t *init_assign,
              const double *bases, RunPlan &plan, std::string &err) {
@@ -518,7 +575,7 @@ int plan_run(const HostGraph &g, const fc_params &params, int32_t n_chains, cons
         if (int rc = init_chain(g, p, c, init_assign + (size_t)c * g.n, bases ? bases[c] : p->base, plan, q, seen, err))
             return rc;
     plan.param_hash = hash_params(p, bases, plan);
-    plan.node_recs = g.ring_max == 8 ? pack_records<8>(g, params) : pack_records<16>(g, params);
+    plan.node_recs = g.ring_max == 8 ? pack_records<8>(g, p->frozen, p->n_frozen) : pack_records<16>(g, p->frozen, p->n_frozen);
     if (p->proposal == FC_PROPOSE_RECOM) recom_tables(g, bases ? bases[0] : p->base, plan);
     // the event log (FC_DIAG_SERIES with a capacity) and the traced chains
     if ((p->diag_mask & FC_DIAG_SERIES) && p->event_cap > 0)

@@ -75,4 +75,21 @@ struct RunPlan : RunShape {
 int plan_run(const HostGraph &g, const fc_params &p, int32_t n_chains, const int8_t *init_assign,
              const double *bases, RunPlan &plan, std::string &err);
 
+// The tables of the spanning-tree kernels (RecomParams / SeedParams nbe, eslot): each node's
+// neighbours in ring order with their edge ids, nb_d entries per row, and each edge end's index in
+// the other end's row.  A function of the graph: the ReCom plan and the seed plans share it.
+void neighbour_rows(const HostGraph &g, int32_t &nb_d, std::vector<uint32_t> &nbe, std::vector<uint32_t> &eslot);
+
+// The host half of fc_graph_seed_plans: the argument checks (FC_OK, or an FC_ERR_* code with its
+// message in `err`), the defaults filled in and the bounds clipped to [0, total], the LDS bytes of
+// a plan and the tables that are then uploaded.
+struct SeedPlan {
+    fc_seed_params p{};
+    int64_t pop_total = 0;
+    int32_t npad = 0, chain_lds_bytes = 0, nb_d = 4;
+    std::vector<unsigned char> node_recs;
+    std::vector<uint32_t> nbe, eslot;
+};
+int plan_seed(const HostGraph &g, const fc_seed_params &p, int32_t n_plans, SeedPlan &s, std::string &err);
+
 }  // namespace fc

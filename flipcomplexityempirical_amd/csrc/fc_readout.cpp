@@ -8,6 +8,15 @@
 
 #include "fc_run.h"
 
+// Whether `bytes` more of device memory fit a tenth of what is free: the bound on a buffer that a
+// run keeps and a single call sizes (fc_run.h).
+int fc::fits_free_tenth(size_t bytes, bool &fits) {
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    fits = bytes <= free_b / 10;
+    return FC_OK;
+}
+
 namespace {
 
 // a chain whose event log ran past event_cap has no series to evaluate
@@ -90,15 +99,6 @@ int open_window(fc_run *r, const char *who, int32_t c0, int32_t nc, bool bound_y
     s.log.t_end = r->d_ser_meta + 2 * (size_t)nc;
     s.cut0 = r->d_ser_meta + 3 * (size_t)nc;
     s.nb0 = r->d_ser_meta + 4 * (size_t)nc;
-    return FC_OK;
-}
-
-// Whether `bytes` more of device memory fit a tenth of what is free: the bound on a buffer that a
-// run keeps and a single call sizes.
-int fits_free_tenth(size_t bytes, bool &fits) {
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    fits = bytes <= free_b / 10;
     return FC_OK;
 }
 

@@ -108,12 +108,16 @@ struct EventMarks {
     }
 };
 
+// Whether `bytes` more of device memory fit a tenth of what is free (fc_readout.cpp).
+int fits_free_tenth(size_t bytes, bool &fits);
+
 constexpr size_t kMaxLaunchEvents = 4096;  // per-launch HIP event pairs kept (fc_run_timings)
 
 }  // namespace fc
 
 using fc::DevBuf;
 using fc::fail;
+using fc::fits_free_tenth;
 using fc::fnv1a;
 
 struct fc_run : fc::RunShape {

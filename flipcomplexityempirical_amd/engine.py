@@ -113,6 +113,56 @@ class FlipGraph:
               "fc_graph_heat_rows")
         return nbr.reshape(self.n, width.value), eid.reshape(self.n, width.value)
 
+    def seed_plans(self, k: int, n_plans: int, *, pop_bounds=None, percent: Optional[float] = None, seed: int = 0,
+                   plan_id_offset: int = 0, node_repeats: int = 1, max_attempts: int = 0, max_restarts: int = 0,
+                   strict: bool = True, device: int = 0, timing: bool = False):
+        """``n_plans`` random k-district start plans by recursive spanning-tree bipartition on the
+        device (``fc_graph_seed_plans``, gerrychain's ``recursive_tree_part``):
+        ``(plans, stats)`` with ``plans`` int8 ``[n_plans, n]`` (district ids 0..k-1 in canonical
+        node order, one row per chain of ``FlipRun``) and ``stats`` the per-plan ``attempts``,
+        ``trees``, ``restarts``, ``ok``, ``cut`` and ``nb`` arrays, plus ``kernel`` (the launched
+        instance) and, with ``timing``, ``kernel_ms``.
+
+        The districts' inclusive integer population bounds are ``pop_bounds=(lo, hi)``, or
+        ``percent`` through :func:`graphs.population_bounds` -- give exactly one.  Plan ``i`` is the
+        plan of global id ``plan_id_offset + i`` under ``seed``: it does not depend on the call it
+        is computed in, so ranks that pass disjoint id ranges share one ensemble.  A plan that
+        found no cut within ``max_attempts`` attempts per level (0: 256) in ``max_restarts``
+        restarts (0: 16) has ``ok = 0`` and a row of -1: ``strict`` raises ``RuntimeError`` naming
+        those ids, otherwise read ``stats["ok"]``."""
+        from .graphs import population_bounds
+        if (pop_bounds is None) == (percent is None):
+            raise ValueError("seed_plans: give exactly one of pop_bounds=(lo, hi) and percent")
+        if percent is not None:
+            pop_bounds = population_bounds(int(self.spec.pop.astype(np.int64).sum()), int(k), float(percent))[1]
+        lo, hi = (int(x) for x in pop_bounds)
+        L = _lib.load()
+        prm = _lib.SeedParams()
+        check(L.fc_seed_params_init(ctypes.byref(prm), ctypes.sizeof(prm)), "fc_seed_params_init")
+        _set_fields(prm, k=int(k), pop_lo=lo, pop_hi=hi, seed=int(seed), plan_id_offset=int(plan_id_offset),
+                    device=int(device), node_repeats=int(node_repeats), max_attempts=int(max_attempts),
+                    max_restarts=int(max_restarts))
+        n_plans = int(n_plans)
+        plans = np.zeros((max(n_plans, 0), self.n), dtype=np.int8)
+        st = (_lib.SeedStats * max(n_plans, 1))()
+        ms = ctypes.c_float(0.0)
+        check(L.fc_graph_seed_plans(self.handle, ctypes.byref(prm), n_plans, _p(plans, ctypes.c_int8), st,
+                                    ctypes.byref(ms) if timing else None), "fc_graph_seed_plans")
+        stats: Dict[str, Any] = {f: np.asarray([getattr(st[i], f) for i in range(n_plans)], dtype=np.int64)
+                                 for f, _ in _lib.SeedStats._fields_}
+        name = ctypes.create_string_buffer(96)
+        check(L.fc_seed_kernel_name(name, 96), "fc_seed_kernel_name")
+        stats["kernel"] = name.value.decode()
+        if timing:
+            stats["kernel_ms"] = float(ms.value)
+        failed = np.nonzero(stats["ok"] == 0)[0]
+        if strict and len(failed):
+            ids = ", ".join(str(int(plan_id_offset) + int(i)) for i in failed[:16]) + (", ..." if len(failed) > 16 else "")
+            raise RuntimeError(f"seed_plans: {len(failed)} of {n_plans} plans found no cut within max_attempts / "
+                               f"max_restarts (plan ids {ids}); widen the bounds or raise them, or pass strict=False "
+                               "and read stats['ok']")
+        return plans, stats
+
     def close(self):
         if getattr(self, "handle", None):
             _lib.load().fc_graph_destroy(self.handle)

@@ -299,6 +299,54 @@ int fc_graph_edges(const fc_graph *g, int32_t *eu, int32_t *ev);
 int fc_graph_rings(const fc_graph *g, int32_t *ring, uint64_t *meta);
 void fc_graph_destroy(fc_graph *g);
 
+/* ---- seed plans: random k-district start plans, gerrychain's recursive_tree_part [gc-0.2] on
+ * the device.  A function of the graph: no run is needed, the call is synchronous.
+ * Plan G = plan_id_offset + local index, attempt r = 0 .. max_restarts: every node starts in
+ * district k - 1 (the remainder M); level i = 0 .. k - 2 runs the ReCom proposal's bipartition_tree
+ * on M (the same spanning tree, root and child choices, Philox draw index
+ * 0xFFFFFFFF00000000 | r << 8 | i, chain word G, key seed -- an index no run's draw counter reaches)
+ * with the integer cut rule: node x != root is a cut iff  pop_lo <= s <= pop_hi  and
+ * m pop_lo <= pop(M) - s <= m pop_hi,  s = pop(subtree(x)), m = k - 1 - i the districts the
+ * remainder must still hold.  subtree(child) becomes district i.  A level without a cut after
+ * max_attempts attempts fails the attempt, and attempt r + 1 starts from scratch; a plan that fails
+ * at r = max_restarts has ok = 0 and a row of -1.  Every ok plan has k connected districts inside
+ * [pop_lo, pop_hi], and depends on (graph, k, pop_lo, pop_hi, seed, G, node_repeats, max_attempts,
+ * max_restarts) only: not on how plans are split over calls or devices.                         */
+typedef struct fc_seed_params {
+    uint32_t struct_size;      /* sizeof(fc_seed_params) as the caller compiled it (fc_seed_params_init) */
+    uint32_t abi_version;      /* FC_ABI_VERSION as the caller compiled it                  */
+    int32_t k;                 /* districts, 2..32                                          */
+    int64_t pop_lo, pop_hi;    /* inclusive integer bounds of every district (fc_params.pop_lo / pop_hi) */
+    uint64_t seed;             /* Philox key                                                */
+    uint32_t plan_id_offset;   /* global id of local plan 0                                 */
+    int32_t device;            /* HIP device ordinal                                        */
+    int32_t node_repeats;      /* roots tried per spanning tree; 0: 1                       */
+    int32_t max_attempts;      /* attempts per level; 0: 256                                */
+    int32_t max_restarts;      /* restarts per plan; 0: 16                                  */
+} fc_seed_params;
+typedef struct fc_seed_stats {
+    int64_t attempts, trees;   /* totals over all levels and restarts                       */
+    int32_t restarts;          /* the attempt r the plan ended in                           */
+    int32_t ok;                /* 1: a valid plan; 0: failed (row of -1, cut = nb = 0)      */
+    int32_t cut, nb;           /* |cut edges| and |boundary nodes| of an ok plan            */
+} fc_seed_stats;
+/* Zeroes *p and sets struct_size / abi_version and k = 2, pop_hi = INT64_MAX. */
+int fc_seed_params_init(fc_seed_params *p, uint32_t struct_size);
+/* n_plans plans into assign_out (rows packed to n bytes); stats_out and kernel_ms (the kernel's
+ * device time, HIP events) may be NULL.  Checked on the host before any device call: FC_ERR_ARG for
+ * k outside [2, 32], pop_lo > pop_hi, k pop_lo > the population total or k pop_hi < it, n_plans < 0,
+ * negative node_repeats / max_attempts / max_restarts, max_restarts >= 2^24, or a struct_size / abi_version of
+ * another header; FC_ERR_UNSUPPORTED for n > 8000, a population total above INT32_MAX, a node degree
+ * above 16 or a disconnected graph.  FC_ERR_NOMEM when the plan rows and tables exceed a tenth of
+ * the free device memory: split the call (plan_id_offset keeps the plans the same).            */
+int fc_graph_seed_plans(const fc_graph *g, const fc_seed_params *p, int32_t n_plans,
+                        int8_t *assign_out,       /* [n_plans * n], 0..k-1, -1 rows for failed plans */
+                        fc_seed_stats *stats_out, /* [n_plans] or NULL */
+                        float *kernel_ms);        /* or NULL */
+/* The kernel instance the calling thread's last fc_graph_seed_plans call launched, spelled as
+ * rocprofv3 reports it ("" before the first). */
+int fc_seed_kernel_name(char *buf, int32_t cap);
+
 /* ---- run: replaces Partition(graph, assignment, updaters) + MarkovChain(...) --------- */
 /* init_assign: [n_chains * n] district ids 0..k-1 (one initial plan per chain).
  * bases: [n_chains] per-chain cut_accept base, or NULL for params->base.

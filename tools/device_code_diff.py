@@ -5,7 +5,10 @@ uncompressed offload bundles) and compares, by symbol name, the bytes of every f
 every kernel descriptor (*.kd) of the first build with the second's.  Needs no GPU.  Prints the
 counts and every symbol that is missing or differs (DESIGN.md §5h records a run); for a function
 that differs, both sizes and whether the two disassemblies hold the same instructions, counted by
-mnemonic (so: the same code in another order or other registers)."""
+mnemonic (so: the same code in another order or other registers); for a descriptor that differs,
+whether anything but its kernel_code_entry_byte_offset does (bytes 16-23: the distance from the
+descriptor to the code, which moves with the code object's layout -- a symbol-name string of
+another length is enough -- and says nothing about the kernel)."""
 import collections
 import hashlib
 import os
@@ -62,7 +65,7 @@ def symbols(lib):
                 continue
             _, saddr, soff = secs[ndx]
             body = blob[soff + addr - saddr: soff + addr - saddr + size]
-            syms[name] = (hashlib.sha256(body).hexdigest(), size, path)
+            syms[name] = (hashlib.sha256(body).hexdigest(), size, path, body if name.endswith(".kd") else None)
     return syms
 
 
@@ -83,7 +86,9 @@ for s in missing:
     print("  MOVED", s)
 for s in differ:
     if s.endswith(".kd"):
-        print("  MOVED", s)
+        ka, kb = a[s][3], b[s][3]
+        layout_only = len(ka) == len(kb) == 64 and ka[:16] + ka[24:] == kb[:16] + kb[24:]
+        print("  MOVED", s + (": kernel_code_entry_byte_offset only (layout)" if layout_only else ""))
         continue
     ma, mb = mnemonics(a[s], s), mnemonics(b[s], s)
     print(f"  MOVED {s}: bytes {a[s][1]} -> {b[s][1]}; instructions {sum(ma.values())} -> {sum(mb.values())}, "
