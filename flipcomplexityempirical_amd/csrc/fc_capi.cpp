@@ -424,7 +424,12 @@ static fc::KParams flip_params(const fc_run *r, int64_t n_steps, int64_t max_dra
     k.log1mp = r->d_log1mp;
     k.labels = r->d_labels;
     k.diag = r->p.diag_mask;
-    k.flags = r->p.flags;
+    k.flags = r->p.flags & ~fc::kFlagNbr4;
+    {
+        bool nbr4 = true;
+        for (uint64_t m : r->g.meta) nbr4 = nbr4 && __builtin_popcount((uint32_t)(m >> fc::kMetaNbrShift) & 0xffffu) <= 4;
+        if (nbr4) k.flags |= fc::kFlagNbr4;
+    }
     k.cut_hist = r->d_cut_hist;
     k.nb_hist = r->d_nb_hist;
     k.nb_w = r->nb_w;

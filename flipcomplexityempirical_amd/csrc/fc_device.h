@@ -130,6 +130,20 @@ __device__ __forceinline__ int ring_entry(const uint32_t (&ring)[RMAX / 2], int 
     return (int)((ring[i >> 1] >> (16 * (i & 1))) & 0xffffu);
 }
 
+// ring_entry at a position held in a register (pos < 16; for RMAX = 8 positions 8-15 read cells
+// 0-3): one byte permute per pair of ring words picks the entry's two bytes, selects pick the pair
+template <int RMAX>
+__device__ __forceinline__ int ring_entry_at(const uint32_t (&ring)[RMAX / 2], uint32_t pos) {
+    const uint32_t sel = 0x0c0c0100u + (pos & 3u) * 0x0202u;
+    uint32_t e = __builtin_amdgcn_perm(ring[1], ring[0], sel);
+#pragma unroll
+    for (int k = 1; k < RMAX / 4; ++k) {
+        const uint32_t q = __builtin_amdgcn_perm(ring[2 * k + 1], ring[2 * k], sel);
+        e = ((pos >> 2) == (uint32_t)k) ? q : e;
+    }
+    return (int)e;
+}
+
 using fc::one_run;  // fc_ring.h
 using fc::one_run_flat;
 

@@ -28,6 +28,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <algorithm>
+#include <type_traits>
 
 #include "fc_device.h"
 #include "fc_internal.h"
@@ -71,11 +72,27 @@ __device__ __forceinline__ PhiloxKeys batch_keys(PhiloxKeys keys) {
     }
 }
 
+// The cells a segment pass walks for a slot: its first four neighbours' (two ids to a register: the
+// half-word selects fold into the address adds), or its ring's (the registers phase 2 filled).
+struct NbrCells {
+    static constexpr int N = 4;
+    uint32_t w[2];
+    __device__ __forceinline__ int operator[](int i) const { return (int)((w[i >> 1] >> (16 * (i & 1))) & 0xffffu); }
+};
+template <int RMAX>
+struct RingCells {
+    static constexpr int N = RMAX;
+    const int (&c)[RMAX];
+    __device__ __forceinline__ int operator[](int i) const { return c[i]; }
+};
+
 // keys: the run's Philox round-key table (fc_philox.h), an argument of its own after KParams:
 // with the pointer inside the struct the same loop ran slower (profiles/r09a_flip2_keyarg.txt),
 // and a longer KParams would move every other kernel's hidden arguments.
-template <int RMAX, int NSUB, bool FULL, bool SEARCH, bool XTRA, bool BAND>
-__global__ __launch_bounds__(256, (RMAX == 8 ? 4 : 1)) void flip2_kernel(KParams p, PhiloxKeys keys) {
+// LIST: the segment pass walks each slot's list of (at most four) neighbours instead of its ring's
+// cells; flip2_kernel chooses it per launch, for graphs without a node of more than four.
+template <int RMAX, int NSUB, bool FULL, bool SEARCH, bool XTRA, bool BAND, bool LIST>
+__device__ __forceinline__ void flip2_body(const KParams &p, PhiloxKeys keys) {
     static_assert(FULL || !XTRA, "XTRA is a FULL instance");
     // non-hit draws held per lane: the node stream's four words per Philox call, BAND's rounds
     constexpr int kRV = BAND ? NSUB : 4;
@@ -765,8 +782,53 @@ __global__ __launch_bounds__(256, (RMAX == 8 ? 4 : 1)) void flip2_kernel(KParams
                 const uint64_t K = __ballot(cand1) & lane_range(pos, sg);
                 int x = kWave;  // first lane that must not be committed
                 bool stale_seg = false;
+                // The pass's marks, foreign counts and clears concern a slot's neighbours only.  LIST:
+                // they walk a compact list, not the ring: the cells of the slot's neighbours (their ring
+                // positions come with the record, kMetaPosShift; a slot with fewer than four repeats a
+                // ring cell, masked off by nm) and inA's bits at them (nm's bits 16 and up).  Built here,
+                // not in phase 2: a batch that enters no pass pays nothing.
+                NbrCells nc;
+                const RingCells<RMAX> rc{cell};
+                uint32_t nm = 0u;
+                auto nbr_bits = [&]() { return LIST ? nm : nbr; };       // neighbours, bits as the pass's cells
+                auto ina_bits = [&]() { return LIST ? nm >> 16 : inA; };  // of them, those in A
+                // marks of the cells cl under the mask wm <- lane; the cells' marks above / below lane
+                auto marks_put = [&](const auto &cl, uint32_t wm) {
+                    constexpr int N = std::decay_t<decltype(cl)>::N;
+#pragma unroll
+                    for (int i = 0; i < N; ++i) FC_ST((wm >> i) & 1u, nmark[cl[i]], lane);
+                };
+                auto marks_get = [&](const auto &cl, uint32_t &gt, uint32_t &lt) {
+                    constexpr int N = std::decay_t<decltype(cl)>::N;
+                    int mn[N];
+#pragma unroll
+                    for (int i = 0; i < N; ++i) mn[i] = nmark[cl[i]];
+                    gt = 0u;
+                    lt = 0u;
+#pragma unroll
+                    for (int i = 0; i < N; ++i) {
+                        gt |= (uint32_t)(mn[i] > lane) << i;
+                        lt |= (uint32_t)(mn[i] < lane) << i;
+                    }
+                };
                 if (K) {
                     const bool inK = (K >> lane) & 1ull;
+                    if constexpr (LIST) {
+                        uint32_t npos = (uint32_t)(rec.meta >> kMetaPosShift);
+                        asm volatile("" : "+v"(npos));  // (the build stays here: hoisted, every batch paid for it)
+                        nm = (1u << min((int)__popc(nbr), 4)) - 1u;
+                        uint32_t e[4];
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) {
+                            const uint32_t ps = (npos >> (4 * i)) & 15u;
+                            e[i] = (uint32_t)ring_entry_at<RMAX>(rec.ring, ps);
+                            nm |= ((inA >> ps) & 1u) << (16 + i);
+                        }
+                        nc.w[0] = e[0] | (e[1] << 16);
+                        nc.w[1] = e[2] | (e[3] << 16);
+                        // (opaque: the compiler otherwise sees through the packing and holds the four)
+                        asm volatile("" : "+v"(nc.w[0]), "+v"(nc.w[1]));
+                    }
                     st |= inK ? LF_WROTE : 0u;
                     // marks: smark[node] / nmark[neighbour] = lowest candidate lane (0xff: none).
                     // Every segment pass clears its marks (below), so the first round writes without
@@ -777,32 +839,24 @@ __global__ __launch_bounds__(256, (RMAX == 8 ? 4 : 1)) void flip2_kernel(KParams
                     // slots), beta (later candidates), entering non-hits.  Every lane reads (cells
                     // are valid nodes on idle lanes too), so the reads issue back to back.
                     bool need = inK;
-                    // the neighbour marks only as two ring masks: cells whose mark is above / below
-                    // this lane (8 values live across the rounds made the compiler read them one
-                    // LDS round trip at a time)
+                    // the neighbour marks only as two masks (bits as in nm): cells whose mark is above
+                    // / below this lane (8 values live across the rounds made the compiler read them
+                    // one LDS round trip at a time)
                     int ms = 0xff, mk[kRV];
-                    uint32_t gtm = 0xffffu, ltm = 0u;
+                    uint32_t gtm = 0xffffu, ltm = 0u;  // (no bits at 16 and up: nm's there are not marks)
                     for (;;) {
                         FC_PROF(21, 1);
                         FC_ST(need && ms > lane, smark[v], lane);
-                        const uint32_t wm = need ? (nbr & gtm) : 0u;
-#pragma unroll
-                        for (int i = 0; i < RMAX; ++i) FC_ST((wm >> i) & 1u, nmark[cell[i]], lane);
+                        const uint32_t wm = need ? (nbr_bits() & gtm) : 0u;
+                        if constexpr (LIST) marks_put(nc, wm);
+                        else marks_put(rc, wm);
                         compiler_fence();
                         ms = smark[v];
-                        int mn[RMAX];
-#pragma unroll
-                        for (int i = 0; i < RMAX; ++i) mn[i] = nmark[cell[i]];
 #pragma unroll
                         for (int r = 0; r < kRV; ++r) mk[r] = nmark[rv[r] < 0 ? 0 : (rv[r] & 0xffff)];
-                        gtm = 0u;
-                        ltm = 0u;
-#pragma unroll
-                        for (int i = 0; i < RMAX; ++i) {
-                            gtm |= (uint32_t)(mn[i] > lane) << i;
-                            ltm |= (uint32_t)(mn[i] < lane) << i;
-                        }
-                        const bool again = (ms > lane) | ((nbr & gtm) != 0u);
+                        if constexpr (LIST) marks_get(nc, gtm, ltm);
+                        else marks_get(rc, gtm, ltm);
+                        const bool again = (ms > lane) | ((nbr_bits() & gtm) != 0u);
                         need = need & again;
                         if (!__any(need)) break;
                     }
@@ -810,7 +864,7 @@ __global__ __launch_bounds__(256, (RMAX == 8 ? 4 : 1)) void flip2_kernel(KParams
                     FC_PROF(18, t_mk - t_it1);
                     // alpha: this slot's node or a ring cell is an earlier candidate's node; beta: a
                     // neighbour shared with an earlier candidate
-                    bool conf = (ms < lane) | (inK & ((nbr & ltm) != 0u));
+                    bool conf = (ms < lane) | (inK & ((nbr_bits() & ltm) != 0u));
 #pragma unroll
                     for (int i = 0; i < RMAX; ++i) conf |= (int)smark[cell[i]] < lane;
                     conf &= has;
@@ -876,22 +930,27 @@ __global__ __launch_bounds__(256, (RMAX == 8 ? 4 : 1)) void flip2_kernel(KParams
                     const bool me = (AP >> lane) & 1ull;
                     // foreign-neighbour counts: u sees v leave A (+1 if u in A) and join t (-1 if u
                     // in t); beta leaves every u to one flip of the segment
-                    int oldc[RMAX];
-#pragma unroll
-                    for (int i = 0; i < RMAX; ++i) oldc[i] = fcnt[cell[i]];
-                    compiler_fence();
                     int dnb = 0;
                     // (bit masks, not short-circuit tests: those compiled to a branch per cell)
                     // two districts: a neighbour in A gains v as a foreign neighbour (+1), one in T
                     // loses it (-1); |B| changes by the neighbours whose count leaves or reaches 0
-                    const uint32_t nbm = me ? nbr : 0u;
+                    const uint32_t nbm = me ? nbr_bits() : 0u;
+                    auto counts = [&](const auto &cl) {
+                        constexpr int N = std::decay_t<decltype(cl)>::N;
+                        int oldc[N];
 #pragma unroll
-                    for (int i = 0; i < RMAX; ++i) {
-                        const int nw = oldc[i] + 2 * (int)((inA >> i) & 1u) - 1;
-                        const uint32_t nb_i = (nbm >> i) & 1u;
-                        FC_ST(nb_i, fcnt[cell[i]], nw);
-                        dnb += (min(nw, 1) - min(oldc[i], 1)) & -(int)nb_i;
-                    }
+                        for (int i = 0; i < N; ++i) oldc[i] = fcnt[cl[i]];
+                        compiler_fence();
+#pragma unroll
+                        for (int i = 0; i < N; ++i) {
+                            const int nw = oldc[i] + 2 * (int)((ina_bits() >> i) & 1u) - 1;
+                            const uint32_t nb_i = (nbm >> i) & 1u;
+                            FC_ST(nb_i, fcnt[cl[i]], nw);
+                            dnb += (min(nw, 1) - min(oldc[i], 1)) & -(int)nb_i;
+                        }
+                    };
+                    if constexpr (LIST) counts(nc);
+                    else counts(rc);
                     FC_ST(me, *(uint8_t *)&a[v], 1 - av);
                     FC_ST(me, fcnt[v], nA);
                     const int pkd = me ? ((delta + 32) | ((dnb + 32) << 16)) : 0;
@@ -911,12 +970,18 @@ __global__ __launch_bounds__(256, (RMAX == 8 ? 4 : 1)) void flip2_kernel(KParams
                     compiler_fence();
                 }
                 // clear this pass's marks: the next pass (and the next batch) starts clean.  Every
-                // mark is 0xff between passes, so the lanes that wrote clear their whole ring
-                // (cells that are not neighbours hold 0xff already; padding cells are the node)
+                // mark is 0xff between passes, so the lanes that wrote clear their whole list or ring
+                // (a cell that is no neighbour holds 0xff already, or its own writers clear it too;
+                // padding cells are the node)
                 if (st & LF_WROTE) {
                     smark[v] = 0xff;
+                    if constexpr (LIST) {
 #pragma unroll
-                    for (int i = 0; i < RMAX; ++i) nmark[cell[i]] = 0xff;
+                        for (int i = 0; i < 4; ++i) nmark[nc[i]] = 0xff;
+                    } else {
+#pragma unroll
+                        for (int i = 0; i < RMAX; ++i) nmark[cell[i]] = 0xff;
+                    }
                     st &= ~LF_WROTE;
                 }
                 FC_STAMP(t_sg1);
@@ -1342,6 +1407,23 @@ __global__ __launch_bounds__(256, (RMAX == 8 ? 4 : 1)) void flip2_kernel(KParams
         scp->last_flip = last_flip;
         scp->stuck = stuck;
     }
+}
+
+// The lean node-stream instances of the 8-cell ring carry the body twice: with the neighbour list
+// for a graph whose nodes all have at most four neighbours (kFlagNbr4, set per run from the
+// records), and as it was for any other.  One body taking either form per pass (a wave-uniform test
+// of its candidates' neighbour counts) ran slower than the ring walk alone, and the list cost the
+// FULL, SEARCH and BAND instances scratch they did not have and the lean <16, ...> ones a wave per
+// SIMD (profiles/r10a_flip2_neighbours.txt): those keep the ring walk.
+template <int RMAX, int NSUB, bool FULL, bool SEARCH, bool XTRA, bool BAND>
+__global__ __launch_bounds__(256, (RMAX == 8 ? 4 : 1)) void flip2_kernel(KParams p, PhiloxKeys keys) {
+    if constexpr (RMAX == 8 && !FULL && !SEARCH && !BAND) {
+        if (p.flags & kFlagNbr4) {
+            flip2_body<RMAX, NSUB, FULL, SEARCH, XTRA, BAND, true>(p, keys);
+            return;
+        }
+    }
+    flip2_body<RMAX, NSUB, FULL, SEARCH, XTRA, BAND, false>(p, keys);
 }
 
 int launch_flip2(const KParams &p, const uint32_t *pkeys, int ring_max, void *stream, char *name, size_t name_cap) {

@@ -350,6 +350,7 @@ std::string build_host_graph(int32_t n, const int32_t *row_ptr, const int32_t *c
         if (gamma[v] && g.outer_simple) m |= kMetaGamma;
         m |= (uint64_t)nbr[v] << kMetaNbrShift;
         m |= (uint64_t)link[v] << kMetaLinkShift;
+        m |= meta_nbr_positions(nbr[v]);
         g.meta[v] = m;
         g.n_exact += exact[v] ? 1 : 0;
         g.n_gamma += (gamma[v] && g.outer_simple) ? 1 : 0;

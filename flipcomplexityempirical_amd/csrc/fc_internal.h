@@ -33,7 +33,28 @@ constexpr uint64_t kMetaExact = 1ull << 8;
 constexpr uint64_t kMetaGamma = 1ull << 9;
 constexpr uint64_t kMetaFrozen = 1ull << 10;  // FC_CON_FIXED: endpoint of a pinned cut edge (per run)
 constexpr int kMetaNbrShift = 16;
-constexpr int kMetaLinkShift = 32;
+constexpr int kMetaLinkShift = 32;  // 16 bits: readers mask with 0xffff (the positions follow)
+// bits 48-63: the ring positions of the node's first four neighbours (the lowest set bits of the
+// nbr field, in ring order), 4 bits each; kMetaPosNone where the node has fewer.  flip2_kernel's
+// segment pass walks these instead of the ring's cells.
+constexpr int kMetaPosShift = 48;
+constexpr uint32_t kMetaPosNone = 15u;
+// (a real position 15 -- a 16-cell ring -- reads the same; the neighbour count tells them apart)
+// KParams.flags bit 31 (no public FC_FLAG_*; fc_run_create sets it from the records): no node has
+// more than four neighbours, so the four positions name them all (flip2_kernel's LIST form)
+constexpr uint32_t kFlagNbr4 = 1u << 31;
+inline uint64_t meta_nbr_positions(uint32_t nbr) {
+    uint64_t pos = 0;
+    for (int i = 0; i < 4; ++i) {
+        uint32_t p = kMetaPosNone;
+        if (nbr) {
+            p = (uint32_t)__builtin_ctz(nbr);
+            nbr &= nbr - 1u;
+        }
+        pos |= (uint64_t)p << (4 * i);
+    }
+    return pos << kMetaPosShift;
+}
 
 // Device node record: everything one proposal needs about its node, in one cache sector.
 // ring[] holds int16 node ids packed two per u32, padded with the node itself.
