@@ -8,7 +8,7 @@
         //   p                .max_attempts, .node_repeats, .seed_lo, .seed_hi, .eu, .ev, .eslot;
         //   trees_tot        the spanning-tree counter (int64_t, incremented per tree);
         //   RMAX, lane, n, npad, G, NB, nq, kScanU and the LDS arrays best, spop, par, comp, order,
-        //   tadj with tadj_or, laid out as in fc_recom_body.h (recom_lds_bytes).
+        //   tadj with tadj_or, laid out by fc_lds.h's recom_lds.
         // It leaves: attempts made, tree (the last tree's index), root and child (-1: no cut within
         // p.max_attempts), p0 = pop(subtree(child)), and with a child the sign bit of spop[x] set
         // on subtree(child) -- spop[x] is defined for the nodes of M only.
@@ -214,7 +214,7 @@
             // the tree's adjacency as a CSR in the Boruvka keys' space (dead until the subtree sums):
             // offsets by a wave scan of the tree degrees, neighbour ids from the ring slots
             int16_t *toff = (int16_t *)best;       // [n + 1]
-            int16_t *tnb = toff + ((n + 2) & ~1);  // [2 (|M| - 1)]
+            int16_t *tnb = toff + recom_csr_first(n);  // [2 (|M| - 1)]
             {
                 int ob = 0;
                 for (int x0 = 0; x0 < n; x0 += kWave) {
@@ -279,8 +279,10 @@
                         const int incl = wave_scan_incl(nch);
                         int pos = nb_end + incl - nch;
                         nb_end += __builtin_amdgcn_readlane(incl, kWave - 1);
-                        // every child read issued at once (entries past o1 stay inside the keys'
-                        // space: tnb has room for 4 npad - n - 2 >= 2 n + RMAX of them)
+                        // every child read issued at once.  The written entries end before par;
+                        // the up to RMAX - 1 read past o1 run into par where npad - n < 3 (RMAX =
+                        // 16: 5) and always end before comp, in the chain's own slice; their
+                        // values are discarded (tests/native/lds_layout_check.cpp)
                         int yv[RMAX];
 #pragma unroll
                         for (int j = 0; j < RMAX; ++j) yv[j] = tnb[o0 + j];

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/flipchain.h"
+#include "fc_lds.h"
 #include "fc_replay.h"
 
 namespace fc {
@@ -232,9 +233,6 @@ struct RecomParams {
     int64_t trace_cap;
     int64_t *prof;                 // [n_chains * kProfSlots] phase cycles (FC_PHASE_PROF builds only)
 };
-// fc_recom.hip's layout: 8 B (keys / tree CSR + parents / subtree populations) + component +
-// order (2 + 2 B) + tree-edge bits (1 B for RMAX = 8, else 2) + assignment (1 B) per node
-inline int recom_lds_bytes(int n, int ring_max) { return (ring_max == 8 ? 14 : 15) * ((n + 15) & ~15); }
 // events [n_chains * ev_cap], ev_cap > 0: the run keeps a move log (FC_DIAG_SERIES) and the logging
 // instance recom_log_kernel runs; it takes both as arguments of its own after RecomParams, so the
 // lean instance's argument layout is what it was.  Null / 0: the lean instance recom_kernel
@@ -242,7 +240,7 @@ int launch_recom(const RecomParams &p, fc_event *events, int64_t ev_cap, int rin
                  size_t name_cap);
 
 // Seed-plan kernel parameters (fc_seed.hip): the graph tables are the ReCom kernel's, the LDS
-// layout and workgroup shape too (recom_lds_bytes, waves_per_block); one wave per plan.
+// layout and workgroup shape too (fc_lds.h recom_lds, waves_per_block); one wave per plan.
 struct SeedParams {
     const void *graph;             // NodeRec<RMAX>[n]
     const uint32_t *nbe;           // [n * nb_d] neighbour rows (RecomParams.nbe)

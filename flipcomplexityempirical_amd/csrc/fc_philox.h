@@ -8,11 +8,7 @@
 
 #include <cmath>
 
-#if defined(__HIPCC__) || defined(__HIP__)
-#define FC_HD __host__ __device__ __forceinline__
-#else
-#define FC_HD inline
-#endif
+#include "fc_lds.h"  // FC_HD
 
 namespace fc {
 

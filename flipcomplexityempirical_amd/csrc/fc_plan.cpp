@@ -196,9 +196,8 @@ int plan_lds(const HostGraph &g, const fc_params *p, RunPlan &r, std::string &er
     r.words = (n + 63) / 64;
     if (g.max_degree > 16)  // dev::wave_bfs labels each old neighbour with a 4-bit id
         return bad(err, FC_ERR_UNSUPPORTED, "fc_run_create: node degree above 16");
-    if (recom)   // fc_recom.hip: keys / tree CSR + parents / subtree populations, component /
-                 // levels, order, tree-edge bits, a
-        r.chain_lds_bytes = recom_lds_bytes(n, g.ring_max);
+    if (recom)   // fc_recom.hip takes its pointers from the same layout (fc_lds.h)
+        r.chain_lds_bytes = (int32_t)recom_lds<size_t>(0, r.npad, R).end;
     else if (k == 2)  // fc_flip2.hip: a, fcnt, thresholds, 3 BFS bitmaps, slots, commit marks (2 npad + 16),
                       // wait / tally queue (24 B per entry), launch start time, pace, first queued yield,
                       // tally-log length, launch's first yield (40) (sec11: 10,016 B, so 16 chains still
@@ -554,7 +553,7 @@ int plan_seed(const HostGraph &g, const fc_seed_params &p, int32_t n_plans, Seed
     s.p.max_restarts = p.max_restarts > 0 ? p.max_restarts : 16;
     s.pop_total = total;
     s.npad = (g.n + 15) & ~15;
-    s.chain_lds_bytes = (recom_lds_bytes(g.n, g.ring_max) + 15) & ~15;
+    s.chain_lds_bytes = ((int32_t)recom_lds<size_t>(0, s.npad, g.ring_max).end + 15) & ~15;
     s.node_recs = g.ring_max == 8 ? pack_records<8>(g, nullptr, 0) : pack_records<16>(g, nullptr, 0);
     neighbour_rows(g, s.nb_d, s.nbe, s.eslot);
     return FC_OK;

@@ -14,22 +14,13 @@
     const int n = p.n, E = p.n_edges;
     const int npad = (n + 15) & ~15;
     unsigned char *base = smem + (size_t)wv * p.chain_lds_bytes;
-    // LDS layout (recom_lds_bytes: 14 B per node for RMAX = 8, 15 for 16; the kernel is
-    // latency-bound, so the chains a CU holds set its rate):
-    //   [0, 8 npad)   Boruvka keys; then the tree's CSR [0, 6 npad) and the BFS parents
-    //                 [6 npad, 8 npad); then subtree populations [0, 4 npad) (sign bit: subset mark)
-    //   comp          component; then level starts
-    //   order         hook targets; then BFS order
-    //   tadj          tree edges (bit k: neighbour row entry k)
-    //   a             assignment
+    const auto lds = recom_lds(base, npad, RMAX);  // the chain's arrays (fc_lds.h)
     using TAdj = typename std::conditional<RMAX == 8, uint8_t, uint16_t>::type;
-    uint64_t *best = (uint64_t *)base;
-    int32_t *spop = (int32_t *)best;
-    int16_t *par = (int16_t *)(base + 6 * (size_t)npad);
-    int16_t *comp = (int16_t *)(best + npad);
-    int16_t *order = comp + npad;
-    TAdj *tadj = (TAdj *)(order + npad);
-    int8_t *a = (int8_t *)(tadj + npad);
+    uint64_t *best = (uint64_t *)lds.keys;
+    int32_t *spop = (int32_t *)lds.keys;
+    int16_t *par = (int16_t *)lds.par, *comp = (int16_t *)lds.comp, *order = (int16_t *)lds.order;
+    TAdj *tadj = (TAdj *)lds.tadj;
+    int8_t *a = (int8_t *)lds.a;
     // tree-edge bits by 32-bit LDS atomics on the word holding the node's entry
     auto tadj_or = [&](int x, uint32_t bits) {
         constexpr int kPer = 4 / (int)sizeof(TAdj);

@@ -3,7 +3,7 @@
 // (include/flipchain.h fc_graph_seed_plans).
 //
 // One plan per wavefront; the plan's assignment and the spanning-tree working set live in LDS,
-// in the ReCom kernel's layout (recom_lds_bytes).  Attempt r of a plan labels every node k - 1
+// in the ReCom kernel's layout (fc_lds.h recom_lds).  Attempt r of a plan labels every node k - 1
 // (the remainder M) and cuts one district off M per level i = 0 .. k - 2: the ReCom proposal's
 // bipartition_tree on M -- fc_bipartition.h, the text the ReCom kernels include -- with the cut
 // rule  lo <= s <= hi  and  m lo <= pop(M) - s <= m hi  (m = k - 1 - i more districts must fit the
@@ -46,16 +46,13 @@ __global__ __launch_bounds__(256) void seed_kernel(SeedParams p) {
     if (c >= p.n_plans) return;
     const int n = p.n, k = p.k;
     const int npad = (n + 15) & ~15;
-    unsigned char *base = smem + (size_t)wv * p.chain_lds_bytes;
-    // the ReCom kernel's LDS layout (fc_recom_body.h)
+    const auto lds = recom_lds(smem + (size_t)wv * p.chain_lds_bytes, npad, RMAX);  // the plan's arrays (fc_lds.h)
     using TAdj = typename std::conditional<RMAX == 8, uint8_t, uint16_t>::type;
-    uint64_t *best = (uint64_t *)base;
-    int32_t *spop = (int32_t *)best;
-    int16_t *par = (int16_t *)(base + 6 * (size_t)npad);
-    int16_t *comp = (int16_t *)(best + npad);
-    int16_t *order = comp + npad;
-    TAdj *tadj = (TAdj *)(order + npad);
-    int8_t *a = (int8_t *)(tadj + npad);
+    uint64_t *best = (uint64_t *)lds.keys;
+    int32_t *spop = (int32_t *)lds.keys;
+    int16_t *par = (int16_t *)lds.par, *comp = (int16_t *)lds.comp, *order = (int16_t *)lds.order;
+    TAdj *tadj = (TAdj *)lds.tadj;
+    int8_t *a = (int8_t *)lds.a;
     auto tadj_or = [&](int x, uint32_t bits) {
         constexpr int kPer = 4 / (int)sizeof(TAdj);
         atomicOr((uint32_t *)tadj + x / kPer, bits << (8 * (int)sizeof(TAdj) * (x % kPer)));
