@@ -395,14 +395,12 @@ static fc::KParams flip_params(const fc_run *r, int64_t n_steps, int64_t max_dra
     k.n_chains = r->n_chains;
     k.k = r->p.k;
     k.popk = r->d_popk;
-    k.all_exact = r->g.n_exact == r->g.n ? 1 : 0;
     k.dgraph = r->dgraph ? 1 : 0;
     k.mcnt = r->d_mcnt;
     k.ngk = r->d_ngk;
     k.wmax = r->wmax > 0 ? r->wmax : 1;
     k.wdyn = r->p.k > 2 && r->wmax <= 0 ? 1 : 0;
     k.nfh = r->d_nfh;
-    k.band = r->d_sbits ? 1 : 0;
     k.sbits = r->d_sbits;
     k.band_step0 = 1;
     while (k.band_step0 * 2 < r->words) k.band_step0 *= 2;
@@ -424,12 +422,7 @@ static fc::KParams flip_params(const fc_run *r, int64_t n_steps, int64_t max_dra
     k.log1mp = r->d_log1mp;
     k.labels = r->d_labels;
     k.diag = r->p.diag_mask;
-    k.flags = r->p.flags & ~fc::kFlagNbr4;
-    {
-        bool nbr4 = true;
-        for (uint64_t m : r->g.meta) nbr4 = nbr4 && __builtin_popcount((uint32_t)(m >> fc::kMetaNbrShift) & 0xffffu) <= 4;
-        if (nbr4) k.flags |= fc::kFlagNbr4;
-    }
+    k.flags = (r->p.flags & ~fc::kFlagNbr4) | (r->nbr4 ? fc::kFlagNbr4 : 0u);
     k.cut_hist = r->d_cut_hist;
     k.nb_hist = r->d_nb_hist;
     k.nb_w = r->nb_w;
@@ -451,10 +444,8 @@ static fc::KParams flip_params(const fc_run *r, int64_t n_steps, int64_t max_dra
     k.hit_lo = r->p.hit_lo;
     k.hit_hi = r->p.hit_hi;
     // launch tuning (fc_params.tune_*, resolved and checked by fc_run_create; scheduling only)
-    k.nsub = r->tune.nsub;
     k.hit_stop = r->tune.hit_stop;
     k.par_min = r->tune.par_min;
-    k.multi_flip = r->tune.multi ? r->mf_marks : 0;
     k.wait_q = r->tune.wait_q;
     k.wpb = r->tune.wpb;
     k.coop = r->tune.coop ? 1 : 0;
@@ -582,6 +573,9 @@ int fc_run_steps(fc_run *r, int64_t n_steps, int64_t max_draws, void *hip_stream
     if (n_steps < 0) return fail(FC_ERR_ARG, "fc_run_steps: n_steps must be >= 0");
     if (n_steps == 0) return FC_OK;
     HIP_TRY(hipSetDevice(r->p.device));
+    fc::Instance inst;  // chosen per call: a tape can be set and cleared between calls
+    if (!fc::choose_instance(fc::instance_facts(r->g, *r, r->d_tape, r->d_trace), inst))
+        return fail(FC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(hipErrorInvalidValue));
     fc::KParams k = flip_params(r, n_steps, max_draws);
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : r->stream;
 #ifdef FC_PHASE_PROF
@@ -597,7 +591,7 @@ int fc_run_steps(fc_run *r, int64_t n_steps, int64_t max_draws, void *hip_stream
     HIP_TRY(hipEventRecord(evp.first, s));
     if (r->p.proposal == FC_PROPOSE_RECOM) {
         const fc::RecomParams q = recom_params(r, n_steps, max_draws, k.prof);
-        const int e = fc::launch_recom(q, r->d_events, r->ev_cap, r->g.ring_max, s, r->kname, sizeof r->kname);
+        const int e = fc::launch_recom(q, r->d_events, r->ev_cap, inst.recom, s, r->kname, sizeof r->kname);
         if (e != 0) return fail(FC_ERR_HIP, std::string("recom kernel launch: ") + hipGetErrorString((hipError_t)e));
         return finish_launches(r, evp, s);
     }
@@ -635,8 +629,8 @@ int fc_run_steps(fc_run *r, int64_t n_steps, int64_t max_draws, void *hip_stream
             k.eta_parity = (int32_t)(r->n_flip_launches++ & 1);
             HIP_TRY(hipMemsetAsync(r->d_eta + k.eta_parity, 0, sizeof(uint32_t), s));
         }
-        const int e = r->p.k == 2 ? fc::launch_flip2(k, r->d_pkeys, r->g.ring_max, s, r->kname, sizeof r->kname)
-                                    : fc::launch_flipk(k, r->g.ring_max, s, r->kname, sizeof r->kname);
+        const int e = r->p.k == 2 ? fc::launch_flip2(k, r->d_pkeys, inst.flip2, s, r->kname, sizeof r->kname)
+                                    : fc::launch_flipk(k, inst.flipk, s, r->kname, sizeof r->kname);
         if (e != 0) return fail(FC_ERR_HIP, std::string("flip kernel launch: ") + hipGetErrorString((hipError_t)e));
         if (k.tl_len) {  // the launch's logged tallies, applied and the logs emptied
             const int er = fc::launch_tally_reduce(k, r->g.ring_max, s);

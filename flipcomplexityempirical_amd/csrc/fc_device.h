@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "fc_internal.h"
 #include "fc_philox.h"
 #include "fc_ring.h"
@@ -663,6 +665,17 @@ template <typename... P>
 inline void launch_lds(void (*kern)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t s, const P &...p) {
     if (lds > 65536) (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(kern, grid, block, lds, s, p...);
+}
+
+// Host: a runtime value as a compile-time constant -- calls f(std::integral_constant<int, V>{}) for
+// the V in Vs equal to v and returns what it returns; false when none is.  The launchers nest these
+// to map an instance (fc_instance.h) to its template instance, listing per level only the values
+// that exist, so nothing else is instantiated.  The compiler emits the kernels a nest reaches in the
+// reverse of the order its lists name them; the launchers' lists keep each code object's kernels in
+// the order they have had, and with it their pc-relative offsets (tools/device_code_diff.py).
+template <int... Vs, class F>
+inline bool with_value(int v, F &&f) {
+    return ((v == Vs && f(std::integral_constant<int, Vs>{})) || ...);
 }
 
 }  // namespace fc

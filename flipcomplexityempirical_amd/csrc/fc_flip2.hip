@@ -25,7 +25,6 @@
 //   4. the per-yield diagnostics are accumulated lane-parallel from per-slot status bits.
 #include <hip/hip_runtime.h>
 
-#include <cstdio>
 #include <cstdlib>
 #include <algorithm>
 #include <type_traits>
@@ -39,7 +38,7 @@ namespace fc {
 
 using namespace dev;
 
-// SEARCH = false: every node is exact and FC_FLAG_FORCE_BFS is off (p.all_exact), so the run
+// SEARCH = false: every node is exact and FC_FLAG_FORCE_BFS is off (fc_instance.h), so the run
 // rule decides every proposal and the instance carries no search code (its registers are the
 // hot loop's).  XTRA (FULL only): replay tapes, per-proposal traces, accept / constraint
 // variants and frozen nodes; the diagnostics instance without them keeps its registers too.
@@ -1426,7 +1425,8 @@ __global__ __launch_bounds__(256, (RMAX == 8 ? 4 : 1)) void flip2_kernel(KParams
     flip2_body<RMAX, NSUB, FULL, SEARCH, XTRA, BAND, false>(p, keys);
 }
 
-int launch_flip2(const KParams &p, const uint32_t *pkeys, int ring_max, void *stream, char *name, size_t name_cap) {
+int launch_flip2(const KParams &p, const uint32_t *pkeys, const Flip2Instance &inst, void *stream, char *name,
+                 size_t name_cap) {
     // one chain (wave) per workgroup: the dispatcher then deals consecutive chains, whose
     // bases differ, round-robin over the XCDs, CUs and SIMDs, and the short-boundary chains
     // that set the launch time spread more evenly over the SIMDs than four to a workgroup
@@ -1438,55 +1438,27 @@ int launch_flip2(const KParams &p, const uint32_t *pkeys, int ring_max, void *st
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid(blocks), block(kWave * wpb);
     const PhiloxKeys keys = (PhiloxKeys)(uintptr_t)pkeys;  // the run's own table (fc_run_create)
-    // FULL: replay tapes, traces, event logs, histograms, per-node/per-edge tallies or a
-    // hitting-time window; the lean instance keeps its registers for the hot loop.
-    const bool full = p.tape || p.trace || (p.diag & ~(uint32_t)FC_DIAG_WAIT) || p.hit_lo <= p.hit_hi || p.variant;
-    // replay tapes, traces, accept / constraint variants, frozen nodes
-    const bool xtra = p.tape || p.trace || p.variant;
-    // no search code when the run rule decides every proposal (all nodes exact, no forced search)
-    const bool search = !p.all_exact || (p.flags & FC_FLAG_FORCE_BFS);
-#define FC_LAUNCH2B(R, S, F, X, Y, B)                                                                      \
-    do {                                                                                                    \
-        if (name)                                                                                           \
-            snprintf(name, name_cap, "fc::flip2_kernel<%d, %d, %s, %s, %s, %s>", R, S, F ? "true" : "false", \
-                     X ? "true" : "false", Y ? "true" : "false", B ? "true" : "false");                    \
-        launch_lds(flip2_kernel<R, S, F, X, Y, B>, grid, block, lds, s, p, keys);                           \
-    } while (0)
-#define FC_LAUNCH2(R, S, F, X, Y)                        \
-    do {                                                 \
-        if (p.band) FC_LAUNCH2B(R, S, F, X, Y, true);    \
-        else FC_LAUNCH2B(R, S, F, X, Y, false);          \
-    } while (0)
-#define FC_SEARCH2(R, S, F, Y)                    \
-    do {                                          \
-        if (search) FC_LAUNCH2(R, S, F, true, Y);  \
-        else FC_LAUNCH2(R, S, F, false, Y);        \
-    } while (0)
-#define FC_FULL2(R, S)                                \
-    do {                                              \
-        if (xtra) FC_SEARCH2(R, S, true, true);        \
-        else if (full) FC_SEARCH2(R, S, true, false);  \
-        else FC_SEARCH2(R, S, false, false);           \
-    } while (0)
-#define FC_NSUB2(R)                                \
-    switch (p.nsub) {                              \
-        case 1: FC_FULL2(R, 1); break;             \
-        case 2: FC_FULL2(R, 2); break;             \
-        case 4: FC_FULL2(R, 4); break;             \
-        default: return (int)hipErrorInvalidValue; \
-    }
-    if (ring_max == 8) {
-        FC_NSUB2(8)
-    } else if (ring_max == 16) {
-        FC_NSUB2(16)
-    } else {
-        return (int)hipErrorInvalidValue;
-    }
-#undef FC_NSUB2
-#undef FC_FULL2
-#undef FC_SEARCH2
-#undef FC_LAUNCH2
-#undef FC_LAUNCH2B
+    // (FULL, XTRA) is one level -- 0 lean, 1 full, 2 full + xtra: there is no XTRA instance that is not FULL.
+    // (The order of each list keeps the instances' order in the code object: fc_device.h with_value)
+    const bool ok = with_value<16, 8>(inst.ring, [&](auto r) {
+        return with_value<4, 2, 1>(inst.nsub, [&](auto n) {
+            return with_value<0, 1, 2>(inst.xtra ? 2 : inst.full ? 1 : 0, [&](auto l) {
+                return with_value<0, 1>(inst.search, [&](auto x) {
+                    return with_value<0, 1>(inst.band, [&](auto b) {
+                        constexpr int R = decltype(r)::value, S = decltype(n)::value;
+                        constexpr bool F = decltype(l)::value > 0, Y = decltype(l)::value > 1;
+                        constexpr bool X = decltype(x)::value, B = decltype(b)::value;
+                        const Flip2Instance built{R, S, F, X, Y, B};  // what is launched is what is named
+                        if (!(built == inst)) return false;
+                        if (name) format_instance(built, name, name_cap);
+                        launch_lds(flip2_kernel<R, S, F, X, Y, B>, grid, block, lds, s, p, keys);
+                        return true;
+                    });
+                });
+            });
+        });
+    });
+    if (!ok) return (int)hipErrorInvalidValue;
     return (int)hipGetLastError();
 }
 

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/flipchain.h"
+#include "fc_instance.h"
 #include "fc_lds.h"
 #include "fc_replay.h"
 
@@ -151,7 +152,7 @@ struct KParams {
     fc_event *events;           // [n_chains * ev_cap] (FC_DIAG_SERIES)
     int64_t ev_cap;
     int32_t hit_lo, hit_hi;     // hitting-time window on |cut| (lo > hi: off)
-    int32_t nsub;               // max draw rounds of 64 per batch (1, 2, 4)
+    int32_t nsub;               // (unused: the launched instance carries NSUB, fc_instance.h; kept for the layout)
     int32_t hit_stop;           // start another round only while fewer boundary hits than this
     int64_t *prof;              // [n_chains * kProfSlots] phase cycles (FC_PHASE_PROF builds only)
     int32_t par_min;            // k = 2: segment-parallel commit from this many acceptances on
@@ -168,7 +169,7 @@ struct KParams {
     // k > 2 district-graph contiguity rule (every node exact, planar, simple outer face,
     // k <= kMaxKDistrictRule): per chain, face-adjacent cell pairs per district pair and
     // outer-face nodes per district (fc_kernels.hip district_rule)
-    int32_t all_exact;          // every node's contiguity is decided by the local rules (k = 2 run rule)
+    int32_t all_exact;          // (unused: the instance's SEARCH)
     int32_t dgraph;
     int32_t *mcnt;              // [n_chains * k * k] pair counts, cell [min(X, Y) * k + max(X, Y)]
     int32_t *ngk;               // [n_chains * 32] outer-face nodes per district
@@ -183,7 +184,7 @@ struct KParams {
     uint32_t *ctime;            // [n_chains] draws each chain took in its last launch (the dealing key)
     // k = 2 band stream (FC_STREAM_BAND): per chain the band S = b_nodes + neighbours as a
     // bitmap of `words` u64; a draw selects the i-th member (fc_flip2.hip)
-    int32_t multi_flip;         // k > 2 district-rule instance: several independent flips per commit pass
+    int32_t multi_flip;         // (unused: the instance's MF)
     // k = 2 full diagnostics: the per-flip tallies of the flushed wait / tally queue, logged per
     // chain (two coalesced stores per entry) and applied by tally_reduce after the launch, so
     // the chain's serial stream carries no global atomics (fc_flip2.hip tally_flush).  A full
@@ -192,7 +193,7 @@ struct KParams {
     int64_t *tl_t0;             // [n_chains] yield index at the launch's start (entries hold t - t0)
     int64_t *tl_len;            // [n_chains] entries logged this launch
     int64_t tl_cap;             // entries per chain
-    int32_t band;
+    int32_t band;               // (unused: the instance's BAND)
     int32_t band_step0;         // largest power of two below `words` (rank search over the words)
     uint64_t *sbits;            // [n_chains * words]
 };
@@ -234,10 +235,10 @@ struct RecomParams {
     int64_t *prof;                 // [n_chains * kProfSlots] phase cycles (FC_PHASE_PROF builds only)
 };
 // events [n_chains * ev_cap], ev_cap > 0: the run keeps a move log (FC_DIAG_SERIES) and the logging
-// instance recom_log_kernel runs; it takes both as arguments of its own after RecomParams, so the
-// lean instance's argument layout is what it was.  Null / 0: the lean instance recom_kernel
-int launch_recom(const RecomParams &p, fc_event *events, int64_t ev_cap, int ring_max, void *stream, char *name,
-                 size_t name_cap);
+// instance recom_log_kernel runs (inst.log); it takes both as arguments of its own after RecomParams,
+// so the lean instance's argument layout is what it was.  The lean instance recom_kernel reads neither
+int launch_recom(const RecomParams &p, fc_event *events, int64_t ev_cap, const RecomInstance &inst, void *stream,
+                 char *name, size_t name_cap);
 
 // Seed-plan kernel parameters (fc_seed.hip): the graph tables are the ReCom kernel's, the LDS
 // layout and workgroup shape too (fc_lds.h recom_lds, waves_per_block); one wave per plan.
@@ -257,12 +258,14 @@ struct SeedParams {
 int launch_seed(const SeedParams &p, int ring_max, void *stream, char *name, size_t name_cap);
 
 // Launch wrappers.  Return a hipError_t as int.
-// `name` (may be null) receives the launched instance, spelled as rocprofv3 reports it.
-int launch_flipk(const KParams &p, int ring_max, void *stream, char *name, size_t name_cap);  // k > 2 (fc_kernels.hip)
+// `inst`: the instance to launch (fc_instance.h choose_instance); hipErrorInvalidValue for one that
+// does not exist.  `name` (may be null) receives the launched instance, spelled as rocprofv3 reports it.
+int launch_flipk(const KParams &p, const FlipKInstance &inst, void *stream, char *name, size_t name_cap);  // k > 2 (fc_kernels.hip)
 // k = 2 (fc_flip2.hip).  pkeys: [kPhiloxKeyWords] the seed's Philox round keys (fc_philox.h), in
 // device memory; the kernel takes the pointer as an argument of its own after KParams, so the
 // struct (and with it every other kernel's argument layout) does not carry it
-int launch_flip2(const KParams &p, const uint32_t *pkeys, int ring_max, void *stream, char *name, size_t name_cap);
+int launch_flip2(const KParams &p, const uint32_t *pkeys, const Flip2Instance &inst, void *stream, char *name,
+                 size_t name_cap);
 // k = 2 full diagnostics: apply every chain's tally log (KParams tl_*) to the per-chain
 // histograms / per-node / per-edge arrays and reset the logs (fc_tally.hip)
 int launch_tally_reduce(const KParams &p, int ring_max, void *stream);

@@ -26,8 +26,6 @@
 #include <algorithm>
 #include <cstdlib>
 
-#include <cstdio>
-
 #include "fc_internal.h"
 #include "fc_philox.h"
 #include "fc_device.h"
@@ -1389,7 +1387,7 @@ __global__ __launch_bounds__(256, (RMAX == 8 ? FC_K_WAVES8 : 1)) void flip_kerne
     }
 }
 
-int launch_flipk(const KParams &p, int ring_max, void *stream, char *name, size_t name_cap) {
+int launch_flipk(const KParams &p, const FlipKInstance &inst, void *stream, char *name, size_t name_cap) {
     // one chain (wave) per workgroup, as in fc_flip2.hip (C3 on one MI355X: 1.35e9 proposals/s
     // against 1.29e9 with four chains per workgroup); tune_chains_per_block = 2 / 4 restores larger ones
     const int wpb = p.wpb;  // fc_params.tune_chains_per_block (resolved by fc_run_create)
@@ -1398,61 +1396,29 @@ int launch_flipk(const KParams &p, int ring_max, void *stream, char *name, size_
     hipStream_t s = (hipStream_t)stream;
     // cooperative search: one chain per 256-thread workgroup (wave 0 + three search helpers)
     const dim3 grid(blocks), block(p.coop ? kWave * kWavesPerBlock : kWave * wpb);
-    // FULL: replay tapes, traces, event logs, histograms, per-node/per-edge tallies or a
-    // hitting-time window; the lean instance (proposals, steps, sums, waits) keeps its
-    // register budget for the hot loop.
-    const bool full = p.tape || p.trace || (p.diag & ~(uint32_t)FC_DIAG_WAIT) || p.hit_lo <= p.hit_hi;
-#define FC_LAUNCHM(R, S, K, F, M)                                                                       \
-    do {                                                                                                \
-        if (name)                                                                                       \
-            snprintf(name, name_cap, "fc::flip_kernel<%d, %d, %d, %s, %d>", R, S, K, F ? "true" : "false", \
-                     (int)(M));                                                                         \
-        launch_lds(flip_kernel<R, S, K, F, M>, grid, block, lds, s, p);                                 \
-    } while (0)
-    // the multi-flip instance: district-graph rule, when the run asks for it
-    // (1: hashed marks; 2: exact marks, when fc_run_create found room for a byte per node)
-#define FC_LAUNCH(R, S, K, F)                                                     \
-    do {                                                                          \
-        if (K == 3 && p.multi_flip == 2) FC_LAUNCHM(R, S, K, F, (K == 3 ? 2 : 0)); \
-        else if (K == 3 && p.multi_flip) FC_LAUNCHM(R, S, K, F, (K == 3 ? 1 : 0)); \
-        else FC_LAUNCHM(R, S, K, F, 0);                                            \
-    } while (0)
-#define FC_FULL_SWITCH(R, S, K)                          \
-    do {                                                 \
-        if (full) FC_LAUNCH(R, S, K, true);              \
-        else FC_LAUNCH(R, S, K, false);                  \
-    } while (0)
-#define FC_NSUB_SWITCH(R, K)                          \
-    switch (p.nsub) {                                 \
-        case 1: FC_FULL_SWITCH(R, 1, K); break;       \
-        case 2: FC_FULL_SWITCH(R, 2, K); break;       \
-        case 4: FC_FULL_SWITCH(R, 4, K); break;       \
-        default: return (int)hipErrorInvalidValue;    \
-    }
-    // (p.dgraph is off under FC_FLAG_FORCE_BFS, and coop needs it off)
-    if (ring_max == 8) {
-        if (p.coop) {
-            FC_NSUB_SWITCH(8, 1)
-        } else if (p.dgraph) {
-            FC_NSUB_SWITCH(8, 3)
-        } else {
-            FC_NSUB_SWITCH(8, 0)
-        }
-    } else if (ring_max == 16) {
-        if (p.coop) {
-            FC_NSUB_SWITCH(16, 1)
-        } else if (p.dgraph) {
-            FC_NSUB_SWITCH(16, 3)
-        } else {
-            FC_NSUB_SWITCH(16, 0)
-        }
-    } else {
-        return (int)hipErrorInvalidValue;
-    }
-#undef FC_NSUB_SWITCH
-#undef FC_FULL_SWITCH
-#undef FC_LAUNCH
-#undef FC_LAUNCHM
+    // MF is listed per KM: only the district-rule instance KM = 3 has multi-flip forms.
+    // (The order of each list keeps the instances' order in the code object: fc_device.h with_value)
+    const bool ok = with_value<16, 8>(inst.ring, [&](auto r) {
+        return with_value<0, 3, 1>(inst.km, [&](auto k) {
+            return with_value<4, 2, 1>(inst.nsub, [&](auto n) {
+                return with_value<0, 1>(inst.full, [&](auto f) {
+                    auto launch = [&](auto m) {
+                        constexpr int R = decltype(r)::value, S = decltype(n)::value, K = decltype(k)::value;
+                        constexpr int M = decltype(m)::value;
+                        constexpr bool F = decltype(f)::value;
+                        const FlipKInstance built{R, S, K, F, M};  // what is launched is what is named
+                        if (!(built == inst)) return false;
+                        if (name) format_instance(built, name, name_cap);
+                        launch_lds(flip_kernel<R, S, K, F, M>, grid, block, lds, s, p);
+                        return true;
+                    };
+                    if constexpr (decltype(k)::value == 3) return with_value<0, 1, 2>(inst.mf, launch);
+                    else return with_value<0>(inst.mf, launch);
+                });
+            });
+        });
+    });
+    if (!ok) return (int)hipErrorInvalidValue;
     return (int)hipGetLastError();
 }
 

@@ -575,6 +575,8 @@ int plan_run(const HostGraph &g, const fc_params &params, int32_t n_chains, cons
             return rc;
     plan.param_hash = hash_params(p, bases, plan);
     plan.node_recs = g.ring_max == 8 ? pack_records<8>(g, p->frozen, p->n_frozen) : pack_records<16>(g, p->frozen, p->n_frozen);
+    plan.nbr4 = true;
+    for (uint64_t m : g.meta) plan.nbr4 = plan.nbr4 && __builtin_popcount((uint32_t)(m >> kMetaNbrShift) & 0xffffu) <= 4;
     if (p->proposal == FC_PROPOSE_RECOM) recom_tables(g, bases ? bases[0] : p->base, plan);
     // the event log (FC_DIAG_SERIES with a capacity) and the traced chains
     if ((p->diag_mask & FC_DIAG_SERIES) && p->event_cap > 0)
@@ -583,6 +585,18 @@ int plan_run(const HostGraph &g, const fc_params &params, int32_t n_chains, cons
         plan.p.diag_mask &= ~FC_DIAG_SERIES;
     plan.p.trace_chains = p->trace_chains > 0 && p->trace_cap > 0 ? std::min(p->trace_chains, n_chains) : 0;
     return FC_OK;
+}
+
+InstanceFacts instance_facts(const HostGraph &g, const RunShape &r, bool tape, bool trace) {
+    // (line for line with the struct)
+    return {r.p.proposal == FC_PROPOSE_RECOM ? Family::kRecom : r.p.k == 2 ? Family::kFlip2 : Family::kFlipK,
+            g.ring_max, r.tune.nsub,
+            tape, trace, r.p.hit_lo <= r.p.hit_hi,
+            r.p.diag_mask, r.p.flags,
+            r.variant, g.n_exact == g.n, r.p.stream == FC_STREAM_BAND,
+            r.tune.coop != 0, r.dgraph, r.tune.multi != 0,
+            r.mf_marks,
+            r.ev_cap > 0};
 }
 
 }  // namespace fc

@@ -47,6 +47,7 @@ struct RunShape {
     int64_t ev_cap = 0;          // FC_DIAG_SERIES: events kept per chain (0: no event log)
     uint64_t param_hash = 0;     // FNV-1a of every trajectory-determining parameter (checkpoint check)
     bool variant = false;        // accept / constraint variants (FULL k = 2 instance)
+    bool nbr4 = false;           // no node has more than four neighbours (kFlagNbr4), from the records
     RunTune tune{};
     std::vector<double> bases0;        // [n_chains] the base each chain was created with
     std::vector<int64_t> pop_bounds;   // [2 * n_chains]
@@ -74,6 +75,10 @@ struct RunPlan : RunShape {
 // `p`, `init_assign` non-null and n_chains > 0 are the caller's to check.
 int plan_run(const HostGraph &g, const fc_params &p, int32_t n_chains, const int8_t *init_assign,
              const double *bases, RunPlan &plan, std::string &err);
+
+// What choose_instance (fc_instance.h) reads of a run.  A tape can be set and cleared after creation,
+// so fc_run_steps asks at each call: `tape` / `trace`: a replay tape / a trace buffer is set now.
+InstanceFacts instance_facts(const HostGraph &g, const RunShape &r, bool tape, bool trace);
 
 // The tables of the spanning-tree kernels (RecomParams / SeedParams nbe, eslot): each node's
 // neighbours in ring order with their edge ids, nb_d entries per row, and each edge end's index in

@@ -22,7 +22,6 @@
 // a ReCom run on a graph whose population total exceeds INT32_MAX (fc_plan.cpp).
 #include <hip/hip_runtime.h>
 
-#include <cstdio>
 #include <type_traits>
 
 #include "fc_device.h"
@@ -58,24 +57,26 @@ __global__ __launch_bounds__(256) void recom_log_kernel(RecomParams p, fc_event 
 
 }  // namespace
 
-int launch_recom(const RecomParams &p, fc_event *events, int64_t ev_cap, int ring_max, void *stream, char *name,
-                 size_t name_cap) {
+int launch_recom(const RecomParams &p, fc_event *events, int64_t ev_cap, const RecomInstance &inst, void *stream,
+                 char *name, size_t name_cap) {
     const int wpb = waves_per_block(p.chain_lds_bytes);
     const int blocks = (p.n_chains + wpb - 1) / wpb;
     const size_t lds = (size_t)p.chain_lds_bytes * wpb;
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid(blocks), block(kWave * wpb);
-    const bool log = events && ev_cap > 0;
-#define FC_LAUNCH_R(R)                                                                                       \
-    do {                                                                                                     \
-        if (name) snprintf(name, name_cap, log ? "fc::recom_log_kernel<%d>" : "fc::recom_kernel<%d>", R);    \
-        if (log) launch_lds(recom_log_kernel<R>, grid, block, lds, s, p, events, ev_cap);                     \
-        else launch_lds(recom_kernel<R>, grid, block, lds, s, p);                                            \
-    } while (0)
-    if (ring_max == 8) FC_LAUNCH_R(8);
-    else if (ring_max == 16) FC_LAUNCH_R(16);
-    else return (int)hipErrorInvalidValue;
-#undef FC_LAUNCH_R
+    const bool ok = with_value<16, 8>(inst.ring, [&](auto r) {  // (the lists' order: fc_device.h with_value)
+        return with_value<0, 1>(inst.log, [&](auto l) {
+            constexpr int R = decltype(r)::value;
+            constexpr bool LOG = decltype(l)::value;
+            const RecomInstance built{R, LOG};  // what is launched is what is named
+            if (!(built == inst)) return false;
+            if (name) format_instance(built, name, name_cap);
+            if constexpr (LOG) launch_lds(recom_log_kernel<R>, grid, block, lds, s, p, events, ev_cap);
+            else launch_lds(recom_kernel<R>, grid, block, lds, s, p);
+            return true;
+        });
+    });
+    if (!ok) return (int)hipErrorInvalidValue;
     return (int)hipGetLastError();
 }
 
