@@ -86,6 +86,22 @@ __device__ __forceinline__ int count_below(uint64_t m) {  // set bits of m below
     return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
 }
 
+// Wave votes as lane-mask algebra.  A predicate over the lanes is held as its 64-bit mask (bit l:
+// true on lane l), and the rule is: vote() takes ONE compare or bit test; conjunction, disjunction,
+// negation and inequality of two predicates are composed on the masks with scalar operations
+// (A & B, A | B, A & ~B, and a != b is A ^ B); a wave-uniform lane range (lane >= lo && lane < hi)
+// is lane_range(lo, hi) / bits_below(hi) and needs no vote; any(x) is vote(x) != 0.  A vote over a
+// bool composed per lane (__ballot(a && b), __any(a && b)) instead makes the compiler turn the
+// combined mask into a 0 / 1 register and compare that with zero: two wave-wide vector
+// instructions that give back the mask it had.
+// vote(p) & vote(q) == vote(p && q) only when both votes run under the same exec mask (a vote
+// reads 0 on the lanes that are off) and q's operand is safe to evaluate on every active lane:
+// nothing short-circuits, so q may not index by a value that only p makes valid.
+// lanes(M) is the way back: this lane's bit of a wave-uniform mask as a bool for a select or a
+// branch; the mask register is used as it is (no shift, no compare).
+__device__ __forceinline__ uint64_t vote(bool p) { return __builtin_amdgcn_ballot_w64(p); }
+__device__ __forceinline__ bool lanes(uint64_t m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
+
 template <int CTRL>
 __device__ __forceinline__ int dpp_mov(int x) {
     return __builtin_amdgcn_update_dpp(0, x, CTRL, 0xf, 0xf, false);

@@ -414,7 +414,7 @@ __device__ __forceinline__ void flip2_body(const KParams &p, PhiloxKeys keys) {
             gen = win;
             int lim = 4 * kWave;  // draws of the window consumed, as an offset bound
             if (tot > 64) {  // the 64th hit closes the batch
-                const int L = __builtin_ctzll(__ballot(incl >= 64));
+                const int L = __builtin_ctzll(vote(incl >= 64));
                 const uint32_t hbL = rlu(hb, L);
                 const int k = 64 - rl32(excl, L);  // its rank among lane L's hits (1-based)
                 uint32_t mk = hbL;  // its word: the k-th set bit of lane L's hits (wave-uniform)
@@ -683,29 +683,40 @@ __device__ __forceinline__ void flip2_body(const KParams &p, PhiloxKeys keys) {
             // be hoisted as lane masks into SGPRs and spilled
             asm volatile("" : "+v"(st), "+v"(inA), "+v"(tmask), "+v"(nbr), "+v"(delta), "+v"(nA), "+v"(av), "+v"(pv),
                          "+v"(v), "+v"(off_l));
+            // The predicates are lane masks (upper-case: bit l is lane l's; fc_device.h vote): one
+            // vote per compare or bit of st, combined with scalar operations; lanes() gives a lane
+            // its bit back where a select needs it.  Every vote of the commit runs with the whole
+            // wave active (the branches around them are wave-uniform), and no vote's operand
+            // indexes memory, so the masks equal the votes over the composed bools.
             // (SEARCH = false: every node exact and no search verdicts -- compile-time constants,
             // so the lean instance carries no undecided-slot logic)
-            const bool hit = (st & LF_HIT) != 0, acc = (st & LF_ACC) != 0, s_lin = (st & LF_SLIN) != 0,
-                       s_cyc = (st & LF_SCYC) != 0, exact = SEARCH ? (st & LF_EXACT) != 0 : true,
-                       gam = (st & LF_GAM) != 0, has = (st & LF_HAS) != 0;
-            const bool prop = hit & (lane >= pos) & (lane < end);
-            // contiguity verdict when the other district does (okT) / does not (okN) touch
+            const uint64_t HIT = vote((st & LF_HIT) != 0u), ACC = vote((st & LF_ACC) != 0u),
+                           SLIN = vote((st & LF_SLIN) != 0u), SCYC = vote((st & LF_SCYC) != 0u),
+                           GAM = vote((st & LF_GAM) != 0u);
+            const uint64_t EXACT = SEARCH ? vote((st & LF_EXACT) != 0u) : ~0ull;
+            const uint64_t HAS = bits_below(ns);  // (LF_HAS is lane < ns)
+            const uint64_t PROP = HIT & lane_range(pos, end);
+            // contiguity verdict when the other district does (OKT) / does not (OKN) touch
             // the outer face -- the outer-face counts are chain-global
-            // (selects, not an if-chain: the chain compiled to nested exec-mask branches)
             // BFS verdict if any; no old-district neighbour: invalid; else the run rule, exact
             // or (not exact) deciding only "one run"
-            const bool bd = SEARCH && (st & ST_BD) != 0, br = SEARCH && (st & ST_BR) != 0, nz = nA != 0;
-            const bool okT = bd ? br : (nz & s_lin);
-            const bool okN = bd ? br : (nz & ((exact & gam) ? s_cyc : s_lin));
-            const bool known = bd | !nz | exact | s_lin;
-            const bool ok = ((av ? ng0 : ng1) > 0) ? okT : okN;
+            const uint64_t BD = SEARCH ? vote((st & ST_BD) != 0u) : 0ull, BR = SEARCH ? vote((st & ST_BR) != 0u) : 0ull;
+            const uint64_t NZ = vote(nA != 0);
+            const uint64_t OKT = (BD & BR) | (~BD & NZ & SLIN);
+            const uint64_t OKN = (BD & BR) | (~BD & NZ & ((EXACT & GAM & SCYC) | (~(EXACT & GAM) & SLIN)));
+            const uint64_t KNOWN = BD | ~NZ | EXACT | SLIN;
+            const uint64_t OT = vote((av ? ng0 : ng1) > 0);
+            const uint64_t OK = (OT & OKT) | (~OT & OKN);
             const int pa = av ? pops1 : pops0, pb = av ? pops0 : pops1;
-            const bool popok = (pa - pv >= pop_lo) & (pb + pv <= pop_hi);
-            bool valid = prop & known & ok & popok;
-            bool acc_now = acc;
-            bool inv_contig = !ok;  // reason of an invalid proposal: contiguity, else "pop"
+            const uint64_t POPOK = vote(pa - pv >= pop_lo) & vote(pb + pv <= pop_hi);
+            uint64_t VALID = PROP & KNOWN & OK & POPOK;
+            uint64_t ACC_NOW = ACC;
+            uint64_t INV_CONTIG = ~OK;  // reason of an invalid proposal: contiguity, else "pop"
             if constexpr (XTRA) {
                 if (p.variant) {
+                    // (the variants' verdicts depend on run-time masks: formed per lane, voted on whole)
+                    const bool gam = lanes(GAM), ok = lanes(OK), popok = lanes(POPOK), prop = lanes(PROP),
+                               known = lanes(KNOWN), acc = lanes(ACC);
                     // Validator members re-draw, accept-callable constraints reject the step
                     // (grid_chain_sec11.py:39-52,81-110,159-165); contiguity / populations as
                     // above, boundary_condition from the outer-face counts, fixed_endpoints
@@ -717,8 +728,8 @@ __device__ __forceinline__ void flip2_body(const KParams &p, PhiloxKeys keys) {
                         return (!(M & FC_CON_CONTIG) || ok) && (!(M & FC_CON_POP) || popok) &&
                                (!(M & FC_CON_BOUNDARY) || b_ok) && (!(M & FC_CON_FIXED) || f_ok);
                     };
-                    valid = prop && known && pass(p.con_valid);
-                    inv_contig = (p.con_valid & FC_CON_CONTIG) && !ok;
+                    VALID = vote(prop && known && pass(p.con_valid));
+                    INV_CONTIG = (p.con_valid & FC_CON_CONTIG) ? ~OK : 0ull;
                     bool au = acc;
                     if (p.accept == FC_ACCEPT_UNIFORM) {
                         au = true;  // random() < 1
@@ -736,10 +747,10 @@ __device__ __forceinline__ void flip2_body(const KParams &p, PhiloxKeys keys) {
                         const double bound = bw * ((double)(nb + dnb_l) / (double)nb);
                         au = (double)mant53(w1, w2) * 0x1p-53 < bound;
                     }
-                    acc_now = pass(p.con_accept) && au;
+                    ACC_NOW = vote(pass(p.con_accept) && au);
                 }
             }
-            const uint64_t C0 = __ballot(valid && acc_now);
+            const uint64_t C0 = VALID & ACC_NOW;
             FC_STAMP(t_it1);
             FC_PROF(8, t_it1 - t_it0);
             if (__popcll(C0) >= p.par_min) {
@@ -755,30 +766,33 @@ __device__ __forceinline__ void flip2_body(const KParams &p, PhiloxKeys keys) {
                 // first lane whose verdict changes under that view closes the segment (it is
                 // itself exact).  Flips committed one at a time (below) leave no marks: they cut
                 // the batch at every lane they affect themselves.
-                const bool cand0 = valid && acc;
+                const uint64_t CAND0 = VALID & ACC;
                 const int dp_l = dp_of(), dg_l = dg_of();
-                const int x0 = cand0 ? dp_l : 0;
+                const int x0 = lanes(CAND0) ? dp_l : 0;
                 const int P = wave_scan_incl(x0) - x0;
-                const int Gp = count_below(__ballot(cand0 && dg_l > 0)) - count_below(__ballot(cand0 && dg_l < 0));
-                const bool ok1 = ((av ? ng0 + Gp : ng1 - Gp) > 0) ? okT : okN;
+                // (dg_l > 0: an outer-face node of district 1; dg_l < 0: one of district 0)
+                const uint64_t AV = vote(av != 0);
+                const int Gp = count_below(CAND0 & GAM & AV) - count_below(CAND0 & GAM & ~AV);
+                const uint64_t OT1 = vote((av ? ng0 + Gp : ng1 - Gp) > 0);
+                const uint64_t OK1 = (OT1 & OKT) | (~OT1 & OKN);
                 const int q0 = pops0 + P, q1 = pops1 - P;
-                const bool valid1 = prop & known & ok1 & ((av ? q1 : q0) - pv >= pop_lo) &
-                                    ((av ? q0 : q1) + pv <= pop_hi);
-                const bool cand1 = valid1 && acc;
-                const uint64_t MM = __ballot(prop && cand1 != cand0);
-                const uint64_t UU = __ballot(prop && !known);
+                const uint64_t VALID1 = PROP & KNOWN & OK1 & vote((av ? q1 : q0) - pv >= pop_lo) &
+                                        vote((av ? q0 : q1) + pv <= pop_hi);
+                const uint64_t CAND1 = VALID1 & ACC;
+                const uint64_t MM = PROP & (CAND1 ^ CAND0);
+                const uint64_t UU = PROP & ~KNOWN;
                 int sg = end;
                 if (MM) sg = min(sg, __builtin_ctzll(MM) + 1);
                 const int u = UU ? __builtin_ctzll(UU) : kWave;
                 if (u < sg) sg = u;
-                uint64_t VAL = __ballot(valid1) & lane_range(pos, sg);
+                uint64_t VAL = VALID1 & lane_range(pos, sg);
                 bool last_step = false;
                 if (__popcll(VAL) >= rem) {  // the launch's last step lies in this segment
                     sg = kth_set_bit(VAL, rem) + 1;
                     VAL &= bits_below(sg);
                     last_step = true;
                 }
-                const uint64_t K = __ballot(cand1) & lane_range(pos, sg);
+                const uint64_t K = CAND1 & lane_range(pos, sg);
                 int x = kWave;  // first lane that must not be committed
                 bool stale_seg = false;
                 // The pass's marks, foreign counts and clears concern a slot's neighbours only.  LIST:
@@ -811,7 +825,7 @@ __device__ __forceinline__ void flip2_body(const KParams &p, PhiloxKeys keys) {
                     }
                 };
                 if (K) {
-                    const bool inK = (K >> lane) & 1ull;
+                    const bool inK = lanes(K);
                     if constexpr (LIST) {
                         uint32_t npos = (uint32_t)(rec.meta >> kMetaPosShift);
                         asm volatile("" : "+v"(npos));  // (the build stays here: hoisted, every batch paid for it)
@@ -838,6 +852,7 @@ __device__ __forceinline__ void flip2_body(const KParams &p, PhiloxKeys keys) {
                     // slots), beta (later candidates), entering non-hits.  Every lane reads (cells
                     // are valid nodes on idle lanes too), so the reads issue back to back.
                     bool need = inK;
+                    uint64_t NEED = K;  // need, as a mask: the rounds end when it is empty
                     // the neighbour marks only as two masks (bits as in nm): cells whose mark is above
                     // / below this lane (8 values live across the rounds made the compiler read them
                     // one LDS round trip at a time)
@@ -855,19 +870,18 @@ __device__ __forceinline__ void flip2_body(const KParams &p, PhiloxKeys keys) {
                         for (int r = 0; r < kRV; ++r) mk[r] = nmark[rv[r] < 0 ? 0 : (rv[r] & 0xffff)];
                         if constexpr (LIST) marks_get(nc, gtm, ltm);
                         else marks_get(rc, gtm, ltm);
-                        const bool again = (ms > lane) | ((nbr_bits() & gtm) != 0u);
-                        need = need & again;
-                        if (!__any(need)) break;
+                        NEED &= vote(ms > lane) | vote((nbr_bits() & gtm) != 0u);
+                        need = lanes(NEED);
+                        if (!NEED) break;
                     }
                     FC_STAMP(t_mk);
                     FC_PROF(18, t_mk - t_it1);
                     // alpha: this slot's node or a ring cell is an earlier candidate's node; beta: a
                     // neighbour shared with an earlier candidate
-                    bool conf = (ms < lane) | (inK & ((nbr_bits() & ltm) != 0u));
+                    uint64_t CONF = vote(ms < lane) | (K & vote((nbr_bits() & ltm) != 0u));
 #pragma unroll
-                    for (int i = 0; i < RMAX; ++i) conf |= (int)smark[cell[i]] < lane;
-                    conf &= has;
-                    const uint64_t XX = __ballot(conf && lane > pos && lane < end);
+                    for (int i = 0; i < RMAX; ++i) CONF |= vote((int)smark[cell[i]] < lane);
+                    const uint64_t XX = CONF & HAS & lane_range(pos + 1, end);
                     if (XX) {
                         x = __builtin_ctzll(XX);
                         stale_seg = true;
@@ -879,13 +893,13 @@ __device__ __forceinline__ void flip2_body(const KParams &p, PhiloxKeys keys) {
                     int t = trunc_off;
 #pragma unroll
                     for (int r = 0; r < kRV; ++r) {
-                        const bool tr = (rv[r] >= 0) & (mk[r] < x) & (mk[r] < (rv[r] >> 16));
-                        const uint64_t TR = __ballot(tr);
+                        // (no draw: rv[r] >> 16 is -1, below every mark)
+                        const uint64_t TR = vote(mk[r] < x) & vote(mk[r] < (rv[r] >> 16));
                         if (TR) t = min(t, rv_off(r, __builtin_ctzll(TR)));
                     }
                     if (t < trunc_off) {
                         trunc_off = t;
-                        const int e2 = __popcll(__ballot(has && off_l < t));
+                        const int e2 = __popcll(HAS & vote(off_l < t));
                         if (e2 < x) x = e2;
                         if (e2 < end) end = e2;  // the batch ends before the first entering draw
                         FC_PROF(14, 1);
@@ -921,12 +935,13 @@ __device__ __forceinline__ void flip2_body(const KParams &p, PhiloxKeys keys) {
                     }
                 }
                 if (x < sg) last_step = false;
-                if (prop && lane < ce) st |= valid1 ? (cand1 ? (ST_VS | ST_AC) : ST_VS) : (ok1 ? ST_IP : ST_IC);
+                if (lanes(PROP & bits_below(ce)))
+                    st |= lanes(VALID1) ? (lanes(CAND1) ? (ST_VS | ST_AC) : ST_VS) : (lanes(OK1) ? ST_IP : ST_IC);
                 rem -= __popcll(VAL & bits_below(ce));
                 const uint64_t AP = K & bits_below(ce);
                 if (AP) {
                     FC_PROF(7, __popcll(AP));
-                    const bool me = (AP >> lane) & 1ull;
+                    const bool me = lanes(AP);
                     // foreign-neighbour counts: u sees v leave A (+1 if u in A) and join t (-1 if u
                     // in t); beta leaves every u to one flip of the segment
                     int dnb = 0;
@@ -1013,21 +1028,21 @@ __device__ __forceinline__ void flip2_body(const KParams &p, PhiloxKeys keys) {
                 continue;
             }
             // ---- one event at a time: the first acceptance or undecided lane -----------------
-            const uint64_t VAL = __ballot(valid);
-            const uint64_t EV = C0 | __ballot(prop && !known);
+            const uint64_t VAL = VALID;
+            const uint64_t EV = C0 | (PROP & ~KNOWN);
             const int f = EV ? __builtin_ctzll(EV) : end;
             const uint64_t segv = VAL & bits_below(f);
             const int nvalid = __popcll(segv);
-            const uint32_t bits = valid ? ST_VS : (inv_contig ? ST_IC : ST_IP);
+            const uint32_t bits = lanes(VALID) ? ST_VS : (lanes(INV_CONTIG) ? ST_IC : ST_IP);
             if (nvalid >= rem) {  // the launch's last step lies before f
                 const int e = kth_set_bit(segv, rem);
-                st |= (prop & (lane <= e)) ? bits : 0u;
+                st |= lanes(PROP & bits_below(e + 1)) ? bits : 0u;
                 rem = 0;
                 end = e + 1;
                 target_hit = true;
                 break;
             }
-            st |= (prop & (lane < f)) ? bits : 0u;
+            st |= lanes(PROP & bits_below(f)) ? bits : 0u;
             rem -= nvalid;
             pos = f;
             if (f >= end) {
@@ -1046,7 +1061,7 @@ __device__ __forceinline__ void flip2_body(const KParams &p, PhiloxKeys keys) {
             FC_PROF(9, t_ap0 - t_it1);
             const int vf = rl32(v, f), Af = rl32(av, f), pvf = rl32(pv, f), df = rl32(delta, f);
             const uint32_t inAf = rlu(inA, f), nbrf = rlu(nbr, f), tmf = rlu(tmask, f);
-            const bool gamf = rl32((int)gam, f) != 0;
+            const bool gamf = (GAM >> f) & 1ull;
             uint32_t rw[RMAX / 2];
 #pragma unroll
             for (int k2 = 0; k2 < RMAX / 2; ++k2) rw[k2] = rlu(rec.ring[k2], f);
@@ -1054,19 +1069,21 @@ __device__ __forceinline__ void flip2_body(const KParams &p, PhiloxKeys keys) {
 #pragma unroll
             for (int k2 = 1; k2 < RMAX / 2; ++k2) sel = ((lane >> 1) == k2) ? rw[k2] : sel;
             const int my_e = (int)((sel >> (16 * (lane & 1))) & 0xffffu);
-            const bool is_nbr = lane < RMAX && ((nbrf >> lane) & 1u);
+            // the flipped node's ring is dealt one cell to a lane: its neighbour, old-district and
+            // target-district bits are wave-uniform lane masks as they stand (no bits at RMAX and up)
+            const uint64_t NBRF = nbrf & ((1u << RMAX) - 1u), INAF = NBRF & inAf, TMF = NBRF & tmf;
+            const bool is_nbr = lanes(NBRF);
             // foreign-neighbour counts: u sees v leave A (+1 if u in A) and join t (-1 if u in t)
-            const int dlt = (int)((inAf >> lane) & 1u) - (int)((tmf >> lane) & 1u);
+            const int dlt = lanes(INAF) ? 1 : (lanes(TMF) ? -1 : 0);
             // (my_e is a valid node on every lane: the read needs no guard, the store goes to the
             // sink off the neighbour lanes)
             const int old = fcnt[my_e];
             FC_ST(is_nbr, fcnt[my_e], old + dlt);
-            const bool enter = is_nbr & (dlt > 0) & (old == 0);
-            const bool leave = is_nbr & (dlt < 0) & (old == 1);
-            bool outS = false;
+            const uint64_t ENTER = INAF & vote(old == 0), LEAVE = TMF & vote(old == 1);
+            uint64_t OUTS = 0ull;
             if constexpr (BAND) {
-                const uint64_t swd = sb[my_e >> 6];
-                outS = enter && !((swd >> (my_e & 63)) & 1ull);
+                const uint64_t swd = sb[my_e >> 6];  // (my_e is a valid node on every lane)
+                OUTS = ENTER & vote(((swd >> (my_e & 63)) & 1ull) == 0ull);
             }
             if (lane == 0) {
                 a[vf] = (int8_t)(1 - Af);
@@ -1077,11 +1094,10 @@ __device__ __forceinline__ void flip2_body(const KParams &p, PhiloxKeys keys) {
             uint32_t eqm = 0;
 #pragma unroll
             for (int i = 0; i < RMAX; ++i) eqm |= (uint32_t)(cell[i] == vf) << i;
-            const bool stale = has & ((v == vf) | (eqm != 0u));
-            const uint64_t aff = __ballot(stale && lane > f && lane < end);
+            const uint64_t aff = (vote(v == vf) | vote(eqm != 0u)) & HAS & lane_range(f + 1, end);
             if (aff) FC_PROF(13, 1);
-            uint64_t ent = __ballot(enter);
-            const int dnb = __popcll(ent) - __popcll(__ballot(leave));
+            const uint64_t ent = ENTER;
+            const int dnb = __popcll(ent) - __popcll(LEAVE);
             // non-hit draws after f whose node just entered the boundary would now propose
             // (the counts written above are read back: a non-hit node had no foreign neighbour
             // when it was drawn, and a flip before f that gave it one has cut the batch already)
@@ -1092,13 +1108,13 @@ __device__ __forceinline__ void flip2_body(const KParams &p, PhiloxKeys keys) {
                 for (int r = 0; r < kRV; ++r) fr[r] = fcnt[rv[r] < 0 ? 0 : (rv[r] & 0xffff)];
 #pragma unroll
                 for (int r = 0; r < kRV; ++r) {
-                    const bool tr = (rv[r] >= 0) & ((rv[r] >> 16) > f) & (fr[r] != 0);
-                    const uint64_t m2 = __ballot(tr);
+                    // (no draw: rv[r] >> 16 is -1, never above f)
+                    const uint64_t m2 = vote((rv[r] >> 16) > f) & vote(fr[r] != 0);
                     if (m2) t_na = min(t_na, rv_off(r, __builtin_ctzll(m2)));
                 }
                 if (t_na < trunc_off) {
                     trunc_off = t_na;
-                    const int e2 = __popcll(__ballot(has && off_l < t_na));
+                    const int e2 = __popcll(HAS & vote(off_l < t_na));
                     if (e2 < end) end = e2;
                     FC_PROF(14, 1);
                 }
@@ -1127,7 +1143,7 @@ __device__ __forceinline__ void flip2_body(const KParams &p, PhiloxKeys keys) {
             FC_STAMP(t_ap1);
             FC_PROF(10, t_ap1 - t_ap0);
             pos = f + 1;
-            const bool f_out = BAND && __ballot(outS) != 0ull;  // S is rebuilt after this flip
+            const bool f_out = BAND && OUTS != 0ull;  // S is rebuilt after this flip
             if (f_out) rebuild = true;
             if (rem == 0) {
                 end = pos;
@@ -1149,14 +1165,12 @@ __device__ __forceinline__ void flip2_body(const KParams &p, PhiloxKeys keys) {
 
         FC_PROF(15, (end == ns && !target_hit && trunc_off == gen) ? 1 : 0);  // every slot committed
         // ---- 4. lane-parallel bookkeeping of the committed draws [0, end) ------------------
-        const bool done = lane < end;
         const bool is_acc = (st & ST_AC) != 0;
-        const bool proposed = (st & LF_HIT) && done;
-        n_acc += __popcll(__ballot(is_acc));
-        n_ic += __popcll(__ballot((st & ST_IC) != 0));
-        n_ip += __popcll(__ballot((st & ST_IP) != 0));
-        const uint64_t ACCM = __ballot(is_acc);
-        const uint64_t VSM = __ballot((st & ST_VS) != 0);
+        const uint64_t ACCM = vote((st & ST_AC) != 0u);
+        const uint64_t VSM = vote((st & ST_VS) != 0u);
+        n_acc += __popcll(ACCM);
+        n_ic += __popcll(vote((st & ST_IC) != 0u));
+        n_ip += __popcll(vote((st & ST_IP) != 0u));
         int ln = lane;  // opaque copy: lane masks derived from it are recomputed, not hoisted and spilled
         asm volatile("" : "+v"(ln));
         const uint64_t later_acc = ACCM & ~bits_below(ln + 1);
@@ -1249,7 +1263,7 @@ __device__ __forceinline__ void flip2_body(const KParams &p, PhiloxKeys keys) {
                 ev_len += __popcll(ACCM);
             }
             if (hit_time < 0 && ACCM) {
-                const uint64_t hm = __ballot(is_acc && cut_after >= p.hit_lo && cut_after <= p.hit_hi);
+                const uint64_t hm = ACCM & vote(cut_after >= p.hit_lo) & vote(cut_after <= p.hit_hi);
                 if (hm) {
                     const int hl = __builtin_ctzll(hm);
                     hit_time = steps0 + __popcll(VSM & bits_below(hl + 1));
@@ -1304,7 +1318,8 @@ __device__ __forceinline__ void flip2_body(const KParams &p, PhiloxKeys keys) {
                 }
             }
             if (trace_on) {
-                const uint64_t PM = __ballot(proposed);
+                const uint64_t PM = vote((st & LF_HIT) != 0u) & bits_below(end);
+                const bool proposed = lanes(PM);
                 const uint64_t mine = ACCM & bits_below(ln + 1);
                 const int src = mine ? 63 - __builtin_clzll(mine) : 0;
                 const int c_j = __shfl(cut_after, src), n_j = __shfl(nb_after, src);

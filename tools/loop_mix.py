@@ -12,6 +12,24 @@ static totals are a usable proxy for the dynamic ones (SQ_INSTS_* of tools/pmc_l
 Usage: python3 tools/loop_mix.py LISTING.s 'flip2_kernel<8, 4, false, false, false, false>'
            [--remarks FILE]   the compile's -Rpass-analysis=kernel-resource-usage output (adds spills)
            [--marker REGEX]   the instruction that separates regions (default: the stamps' clock read)
+           [--by-line]        per source line, largest first (needs a listing with line tables)
+           [--top N]          rows of the per-line table (default 40; 0: all)
+
+--by-line attributes every instruction of each large outermost loop (a kernel that carries its body
+twice, as the lean flip2_kernel instances do, has two batch loops: both are listed) to the source
+file and line of the .loc directive in force, which for inlined code is the innermost callee's
+line: every vote shows under the one line of its helper.  The column pairs counts the round trips
+of a lane mask through a 0 / 1 register: a v_cmp_ne_u32 mask', 0, v whose v was last written, in
+the same block, by v_cndmask_b32 v, 0, 1, mask.  The two instructions give back the mask they
+started from; they are what a vote over a bool composed per lane costs beyond its compares
+(fc_device.h, vote), and each pair is charged to the line of its compare.  The listing it needs:
+
+    hipcc --offload-arch=gfx950 -O3 -std=c++17 -gline-tables-only --cuda-device-only -S \
+        -o flip2.s flipcomplexityempirical_amd/csrc/fc_flip2.hip
+
+Line tables do not change the code: the instruction totals equal those of a listing without them.
+It stands in for a ranking by sampled program counters where those cannot be had: static counts,
+so a line inside a loop that runs often weighs more than its row shows.
 """
 import argparse
 import os
@@ -66,11 +84,11 @@ def kernel_body(lines, flt):
 def parse_blocks(body):
     """Blocks in listing order: {"label", "loops": headers of the enclosing loops, outermost first,
     "insts": mnemonics}.  The loop nest is read from the compiler's block comments."""
-    blocks, cur, pending = [], None, None
+    blocks, cur, pending, loc = [], None, None, None
     for l in body:
         m = re.match(r"^(?:\.L(BB\d+_\d+):|; %bb\.(\d+):)(.*)", l)
         if m:
-            cur = {"label": m.group(1) or f"bb.{m.group(2)}", "loops": [], "insts": [], "self": False}
+            cur = {"label": m.group(1) or f"bb.{m.group(2)}", "loops": [], "insts": [], "full": [], "self": False}
             blocks.append(cur)
             pending = cur
             l = ";" + m.group(3)
@@ -83,11 +101,15 @@ def parse_blocks(body):
                     d = int(re.search(r"Header: Depth=(\d+)", s).group(1))
                     pending["loops"].append((d, pending["label"]))
             continue
+        if s.startswith(".loc"):
+            f = s.split()
+            loc = (int(f[1]), int(f[2]))
         if not s or s.startswith("."):
             continue
         pending = None
         if cur is not None:
             cur["insts"].append(s.split()[0])
+            cur["full"].append((s.split(";")[0].strip(), loc))
     for b in blocks:
         b["loops"] = [h for _, h in sorted(set(b["loops"]))]
     # "in Loop: Header=H Depth=d" names only the innermost loop: complete the chain from H's own
@@ -105,6 +127,50 @@ def mix(insts):
     return t
 
 
+def file_table(lines):
+    """{file number: path} of the listing's .file directives."""
+    out = {}
+    for l in lines:
+        m = re.match(r'^\s*\.file\s+(\d+)\s+"([^"]*)"(?:\s+"([^"]*)")?', l)
+        if m:
+            out[int(m.group(1))] = os.path.join(m.group(2), m.group(3)) if m.group(3) else m.group(2)
+    return out
+
+
+SEL01 = re.compile(r"^v_cndmask_b32\w*\s+(v\d+), 0, 1, (?:s\[|vcc)")
+CMP0 = re.compile(r"^v_cmp_ne_u32\w*\s+(?:s\[\d+:\d+\]|vcc), 0, (v\d+)$")
+DEST = re.compile(r"^v_\w+\s+(v\d+)\b")
+
+
+def by_line(inl, files, top):
+    """Per-line VALU / SALU / LDS table of the blocks inl, and the mask round trips (pairs)."""
+    cols = ("VALU", "SALU", "LDS", "pairs", "all")
+    tab = {}
+    for b in inl:
+        sel01 = set()  # registers holding a mask as 0 / 1
+        for text, loc in b["full"]:
+            t = tab.setdefault(loc, dict.fromkeys(cols, 0))
+            cls = classify(text.split()[0])
+            if cls in t:
+                t[cls] += 1
+            t["all"] += 1
+            if (m := CMP0.match(text)) and m.group(1) in sel01:
+                t["pairs"] += 1
+            if m := DEST.match(text):
+                sel01.discard(m.group(1))
+            if m := SEL01.match(text):
+                sel01.add(m.group(1))
+    rows = sorted(tab.items(), key=lambda kv: (-kv[1]["VALU"] - kv[1]["SALU"] - kv[1]["LDS"], str(kv[0])))
+    fmt = lambda name, t: f"{name:<44}" + "".join(f"{t[c]:>7}" for c in cols)
+    print(f"{'file:line':<44}" + "".join(f"{c:>7}" for c in cols))
+    for loc, t in rows[:top or None]:
+        print(fmt("(no line)" if loc is None else f"{os.path.basename(files.get(loc[0], str(loc[0])))}:{loc[1]}", t))
+    print(fmt(f"total ({len(rows)} lines)", {c: sum(t[c] for t in tab.values()) for c in cols}))
+    for loc, t in rows:
+        if t["pairs"] and rows.index((loc, t)) >= (top or len(rows)):
+            print(fmt(f"  (below the cut) {os.path.basename(files.get(loc[0], str(loc[0])))}:{loc[1]}", t))
+
+
 def row(label, t):
     return f"{label:<28}" + "".join(f"{t[c]:>9}" for c in CLASSES) + f"{sum(t.values()):>9}"
 
@@ -115,6 +181,8 @@ def main():
     ap.add_argument("kernel")
     ap.add_argument("--remarks")
     ap.add_argument("--marker", default=r"^s_memtime")
+    ap.add_argument("--by-line", action="store_true")
+    ap.add_argument("--top", type=int, default=40)
     args = ap.parse_args()
     with open(args.listing) as fh:
         lines = fh.read().splitlines()
@@ -134,6 +202,18 @@ def main():
             top[b["loops"][0]] = top.get(b["loops"][0], 0) + len(b["insts"])
     if not top:
         sys.exit("no loop in this kernel")
+    if args.by_line:
+        if not any(loc for b in blocks for _, loc in b["full"]):
+            sys.exit("no .loc directives: compile the listing with -gline-tables-only")
+        files = file_table(lines)
+        # the batch loops: every outermost loop at least half the largest one's size
+        for h in [h for h in top if 2 * top[h] >= max(top.values())]:
+            inl = [b for b in blocks if b["loops"] and b["loops"][0] == h]
+            print(f"\nloop {h}: {len(inl)} blocks, static instructions by source line")
+            print(f"{'':<28}" + "".join(f"{c:>9}" for c in CLASSES) + f"{'total':>9}")
+            print(row("whole loop", mix([m for b in inl for m in b["insts"]])))
+            by_line(inl, files, args.top)
+        return
     main_loop = max(top, key=top.get)
     inl = [b for b in blocks if b["loops"] and b["loops"][0] == main_loop]
     print(f"\nmain loop {main_loop}: {len(inl)} blocks (static instructions)")
