@@ -54,4 +54,14 @@ FC_HD RecomLds<P> recom_lds(P base, int npad, int ring_max) {
 // int16 index, from keys, of the tree CSR's first entry
 FC_HD int recom_csr_first(int n) { return (n + 2) & ~1; }
 
+// The frame-series kernel (fc_series.hip) stages its tables in LDS: the frame edges' midpoints
+// (double [2 n_frame]), the toggle rows (kFrameLdsWords uint64 per node that has a frame edge) and
+// the node -> row index (int16 [n_nodes]).  Their bytes, or 0 when they do not fit (then the kernel
+// reads them from global memory).  Host arithmetic only.
+constexpr int kFrameLdsWords = 4;  // 64-bit words of a frame-edge mask: up to 256 frame edges
+inline size_t frame_lds_bytes(int32_t n_frame, int32_t n_rows, int32_t n_nodes) {
+    const size_t b = 16 * (size_t)n_frame + 8 * kFrameLdsWords * (size_t)n_rows + 2 * (size_t)n_nodes;
+    return (b <= 48 * 1024 && n_nodes < 32768) ? (b + 15) & ~(size_t)15 : 0;
+}
+
 }  // namespace fc

@@ -452,12 +452,7 @@ __global__ __launch_bounds__(kThreads) void frame_compact_kernel(const int64_t *
     }
 }
 
-// LDS bytes of the staged tables, or 0 when they do not fit (then the kernel reads them from
-// global memory)
-inline size_t frame_lds_bytes(int32_t n_frame, int32_t n_rows, int32_t n_nodes) {
-    const size_t b = 16 * (size_t)n_frame + 8 * kFrameWords * (size_t)n_rows + 2 * (size_t)n_nodes;
-    return (b <= 48 * 1024 && n_nodes < 32768) ? (b + 15) & ~(size_t)15 : 0;
-}
+static_assert(kFrameWords == kFrameLdsWords, "frame_lds_bytes (fc_lds.h) sizes the kernel's mask rows");
 
 }  // namespace
 

@@ -9,9 +9,14 @@
 //   - the tree CSR's offsets and its 2 (n - 1) entries end at or before par, and the speculative
 //     child reads past them (up to RMAX - 1 entries, fc_bipartition.h) end at or before comp,
 //     inside the chain's own slice.
+//   - frame_lds_bytes (the frame-series kernel's staged tables) at the shapes the series tests run,
+//     the 120 x 120 one that does not fit among them; `lds_layout_check frame F R N ...` prints it
+//     for any shapes (tests/test_series_cases.py asks for its case table's).
 // Prints counts and the smallest npad - n from which those reads stay clear of par; exits 1 on any
 // failure.
 #include <cstdio>
+#include <cstdlib>
+#include <string>
 #include <vector>
 
 #include "fc_lds.h"
@@ -98,7 +103,43 @@ static bool check_csr(int n, int R) {
     return read <= L.par;
 }
 
-int main() {
+// frame_lds_bytes at the shapes (frame edges, toggle rows, nodes) the series tests run: the bytes
+// are counted here array by array, and the largest shape is the one that does not fit
+static void check_frame() {
+    struct Shape {
+        const char *name;
+        int n_frame, n_rows, n_nodes;
+        size_t want;
+    };
+    const Shape shapes[] = {{"sec11 frame", 152, 152, 1596, 2432 + 4864 + 3192 + 8},
+                            {"65-cycle, every edge", 65, 65, 65, 1040 + 2080 + 130 + 14},
+                            {"256-cycle, every edge", 256, 256, 256, 4096 + 8192 + 512},
+                            {"120 x 120 grid, 256 disjoint edges", 256, 512, 14400, 0}};
+    for (const Shape &s : shapes) {
+        const size_t got = frame_lds_bytes(s.n_frame, s.n_rows, s.n_nodes);
+        CHECK(got == s.want && got % 16 == 0, "frame %s: %zu bytes, expected %zu", s.name, got, s.want);
+        std::printf("frame_lds_bytes %d %d %d = %zu (%s)\n", s.n_frame, s.n_rows, s.n_nodes, got, s.name);
+    }
+    CHECK(4096 + 16384 + 28800 > 48 * 1024, "the 120 x 120 shape fits after all");
+    // one node either side of the 48 KiB limit
+    CHECK(frame_lds_bytes(0, 0, 24576) == 49152 && frame_lds_bytes(0, 0, 24577) == 0, "48 KiB limit");
+    CHECK(frame_lds_bytes(0, 0, 1) == 16 && frame_lds_bytes(1, 2, 7) == 96, "rounding up to 16");
+    CHECK(frame_lds_bytes(0, 0, 32767) == 0 && frame_lds_bytes(0, 0, 32768) == 0, "n_nodes beyond the limit");
+}
+
+// `lds_layout_check frame F R N [F R N ...]`: frame_lds_bytes of the given shapes, one line each
+static int print_frames(int argc, char **argv) {
+    if ((argc - 2) % 3 != 0) return 2;
+    for (int i = 2; i + 2 < argc; i += 3) {
+        const int f = std::atoi(argv[i]), r = std::atoi(argv[i + 1]), n = std::atoi(argv[i + 2]);
+        std::printf("frame_lds_bytes %d %d %d = %zu\n", f, r, n, frame_lds_bytes(f, r, n));
+    }
+    return 0;
+}
+
+int main(int argc, char **argv) {
+    if (argc > 1 && std::string(argv[1]) == "frame") return print_frames(argc, argv);
+    check_frame();
     std::vector<int> ns;
     for (int n = 1; n <= 200; ++n) ns.push_back(n);
     for (int n : {1596, 2000, 4095, 4096, 10100}) ns.push_back(n);
