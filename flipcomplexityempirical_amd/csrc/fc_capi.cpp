@@ -259,6 +259,21 @@ int fc_run_diag_paths(const fc_run *r, int64_t *tally_log_cap, int64_t *tally_lo
     return FC_OK;
 }
 
+int fc_run_tally_plan(const fc_run *r, int64_t *lds_limit, int32_t *n_passes, uint32_t *lds_masks, int64_t *lds_bytes,
+                      int32_t cap, uint32_t *global_mask) {
+    if (!r || !lds_limit || !n_passes || !global_mask || cap < 0 || (cap > 0 && (!lds_masks || !lds_bytes)))
+        return fail(FC_ERR_ARG, "fc_run_tally_plan: null argument");
+    const fc::TallyPlan &pl = r->tl_plan;
+    *lds_limit = pl.limit;
+    *n_passes = pl.n_passes;
+    *global_mask = pl.gmask;
+    for (int32_t i = 0; i < pl.n_passes && i < cap; ++i) {
+        lds_masks[i] = pl.lmask[i];
+        lds_bytes[i] = pl.bytes[i];
+    }
+    return FC_OK;
+}
+
 int fc_run_create(const fc_graph *gr, const fc_params *p, int32_t n_chains, const int8_t *init_assign,
                   const double *bases, fc_run **out) {
     if (!out) return fail(FC_ERR_ARG, "fc_run_create: null output");
@@ -633,7 +648,7 @@ int fc_run_steps(fc_run *r, int64_t n_steps, int64_t max_draws, void *hip_stream
                                     : fc::launch_flipk(k, inst.flipk, s, r->kname, sizeof r->kname);
         if (e != 0) return fail(FC_ERR_HIP, std::string("flip kernel launch: ") + hipGetErrorString((hipError_t)e));
         if (k.tl_len) {  // the launch's logged tallies, applied and the logs emptied
-            const int er = fc::launch_tally_reduce(k, r->g.ring_max, s);
+            const int er = fc::launch_tally_reduce(k, r->g.ring_max, s, &r->tl_plan);
             if (er != 0) return fail(FC_ERR_HIP, std::string("tally reduce launch: ") + hipGetErrorString((hipError_t)er));
         }
     }

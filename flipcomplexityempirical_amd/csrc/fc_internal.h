@@ -11,6 +11,7 @@
 #include "fc_instance.h"
 #include "fc_lds.h"
 #include "fc_replay.h"
+#include "fc_tally_plan.h"
 
 namespace fc {
 
@@ -267,8 +268,9 @@ int launch_flipk(const KParams &p, const FlipKInstance &inst, void *stream, char
 int launch_flip2(const KParams &p, const uint32_t *pkeys, const Flip2Instance &inst, void *stream, char *name,
                  size_t name_cap);
 // k = 2 full diagnostics: apply every chain's tally log (KParams tl_*) to the per-chain
-// histograms / per-node / per-edge arrays and reset the logs (fc_tally.hip)
-int launch_tally_reduce(const KParams &p, int ring_max, void *stream);
+// histograms / per-node / per-edge arrays and reset the logs (fc_tally.hip).  `used` (may be null)
+// receives the pass plan as launched (fc_tally_plan.h), a pass the device refused demoted in it
+int launch_tally_reduce(const KParams &p, int ring_max, void *stream, TallyPlan *used);
 // chain dealing (fc_deal.hip): order[] = chains by descending key (ctime, the last launch's
 // draws, if `timed`, else the boundary length's complement n - |B|: a short boundary needs
 // many draws per proposal), and the deal counters zeroed, for the next flip launch

@@ -145,6 +145,7 @@ struct fc_run : fc::RunShape {
     DevBuf<uint32_t> d_tl;
     DevBuf<int64_t> d_tl_len, d_tl_t0;
     int64_t tl_want = 0;           // entries per chain the last launch asked for
+    fc::TallyPlan tl_plan;         // the pass plan the last tally reduce launched (fc_run_tally_plan)
     int32_t series_staged = -1;    // last fc_run_frame_series_changes: 1 one staged pass, 0 two passes
     DevBuf<int64_t> d_num_flips, d_part_sum, d_last_flipped;
     DevBuf<int64_t> d_flip_count, d_occ_acc, d_last_accept;  // FC_DIAG_FLIPS_EXACT

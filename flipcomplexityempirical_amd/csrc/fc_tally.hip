@@ -2,12 +2,9 @@
 // per-node and per-edge arrays, after the flip kernel on the same stream.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <utility>
-#include <vector>
-
 #include "fc_internal.h"
 #include "fc_tally.h"
+#include "fc_tally_plan.h"
 
 namespace fc {
 
@@ -17,8 +14,7 @@ namespace fc {
 // with LDS atomics, then added (maxed) into the chain's global rows -- and applies the arrays of
 // `gmask` with global atomics (those too large for any pass).  Global atomics from a separate
 // kernel, for all arrays, took 62 ms per C2 launch: the chains' rows do not stay in L2.
-enum : uint32_t { TR_CUT = 1, TR_NB = 2, TR_EDGE = 4, TR_NF = 8, TR_PS = 16, TR_LF = 32, TR_FC = 64, TR_OCC = 128, TR_LA = 256 };
-constexpr int kTrArrays = 9;
+// (TR_*, kTrArrays and the pass plan: fc_tally_plan.h)
 
 __device__ __forceinline__ int64_t tr_len(const KParams &p, int a) {  // entries of array a per chain
     return a == 0 ? (int64_t)p.n_edges + 1 : a == 1 ? (int64_t)p.n + 1 : a == 2 ? (int64_t)p.n_edges : (int64_t)p.n;
@@ -154,49 +150,20 @@ __global__ __launch_bounds__(1024) void tally_reduce_kernel(KParams p, uint32_t 
     }
 }
 
-int launch_tally_reduce(const KParams &p, int ring_max, void *stream) {
+int launch_tally_reduce(const KParams &p, int ring_max, void *stream, TallyPlan *used) {
     if (!p.tl_len || p.n_chains <= 0) return (int)hipSuccess;
-    // the arrays this run keeps, their per-chain bytes, packed greedily into passes of at most
-    // 160 KiB of LDS (sec11 with every tally: one pass of 139 KiB, one 1024-thread workgroup per
-    // CU: the log is read once); an array above 160 KiB goes to global atomics
-    uint32_t have = 0;
-    if (p.diag & FC_DIAG_HIST) have |= TR_CUT | TR_NB;
-    if (p.diag & FC_DIAG_EDGES) have |= TR_EDGE;
-    if (p.diag & FC_DIAG_FLIPS) have |= TR_NF | TR_PS | TR_LF;
-    if (p.diag & FC_DIAG_FLIPS_EXACT) have |= TR_FC | TR_OCC | TR_LA;
-    auto bytes = [&](int a) -> size_t {
-        return 8 * (size_t)(a == 0 ? p.n_edges + 1 : a == 1 ? p.n + 1 : a == 2 ? p.n_edges : p.n);
-    };
     // the device's LDS per workgroup (gfx950: 160 KiB), queried, not assumed
     int dev = 0, optin = 0;
     if (hipGetDevice(&dev) != hipSuccess ||
         hipDeviceGetAttribute(&optin, hipDeviceAttributeSharedMemPerBlockOptin, dev) != hipSuccess || optin <= 0)
         optin = 65536;
-    const size_t kPass = (size_t)optin, kMaxLds = (size_t)optin;
-    std::vector<std::pair<uint32_t, size_t>> passes;
-    uint32_t gmask = 0;
-    for (int a = 0; a < kTrArrays; ++a) {
-        if (!((have >> a) & 1u)) continue;
-        const size_t b = bytes(a);
-        if (b > kMaxLds) {
-            gmask |= 1u << a;
-            continue;
-        }
-        bool put = false;
-        for (auto &ps : passes)
-            if (ps.second + b <= std::max(kPass, b)) {
-                ps.first |= 1u << a;
-                ps.second += b;
-                put = true;
-                break;
-            }
-        if (!put) passes.emplace_back(1u << a, b);
-    }
-    if (passes.empty()) passes.emplace_back(0u, 0);
-    for (size_t i = 0; i < passes.size(); ++i) {
-        size_t lds = passes[i].second;
-        uint32_t lmask = passes[i].first, g = i == 0 ? gmask : 0u;
-        const int last = i + 1 == passes.size() ? 1 : 0;
+    // the arrays this run keeps in passes of at most that much LDS (fc_tally_plan.h)
+    TallyPlan pl = plan_tally_reduce(p.diag, p.n, p.n_edges, (size_t)optin);
+    const uint32_t gmask = pl.gmask;
+    for (int i = 0; i < pl.n_passes; ++i) {
+        size_t lds = (size_t)pl.bytes[i];
+        uint32_t lmask = pl.lmask[i], g = i == 0 ? gmask : 0u;
+        const int last = i + 1 == pl.n_passes ? 1 : 0;
         const void *fn = ring_max <= 8 ? (const void *)tally_reduce_kernel<8> : (const void *)tally_reduce_kernel<16>;
         if (lds > 65536 &&
             hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
@@ -205,6 +172,9 @@ int launch_tally_reduce(const KParams &p, int ring_max, void *stream) {
             g |= lmask;
             lmask = 0;
             lds = 0;
+            pl.gmask |= pl.lmask[i];  // the plan as launched: an empty pass, its arrays global
+            pl.lmask[i] = 0;
+            pl.bytes[i] = 0;
         }
         if (ring_max <= 8)
             hipLaunchKernelGGL(tally_reduce_kernel<8>, dim3(p.n_chains), dim3(1024), lds, (hipStream_t)stream, p,
@@ -215,6 +185,7 @@ int launch_tally_reduce(const KParams &p, int ring_max, void *stream) {
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return (int)e;
     }
+    if (used) *used = pl;
     return (int)hipSuccess;
 }
 

@@ -895,6 +895,17 @@ class FlipRun:
         return {"tally_log_cap": int(cap.value), "tally_log_wanted": int(want.value),
                 "series_staged": int(staged.value)}
 
+    def tally_plan(self) -> Dict[str, object]:
+        """The pass plan of the last k = 2 tally reduce (``fc_run_tally_plan``): the LDS limit it
+        was planned for, ``passes`` as (LDS array mask, LDS bytes) pairs and the mask of the arrays
+        under global atomics.  No pass: no reduce has run."""
+        limit, n, g = ctypes.c_int64(0), ctypes.c_int32(0), ctypes.c_uint32(0)
+        masks, nbytes = (ctypes.c_uint32 * 9)(), (ctypes.c_int64 * 9)()
+        check(_lib.load().fc_run_tally_plan(self.handle, ctypes.byref(limit), ctypes.byref(n), masks, nbytes, 9,
+                                            ctypes.byref(g)), "fc_run_tally_plan")
+        return {"limit": int(limit.value), "passes": [(int(masks[i]), int(nbytes[i])) for i in range(n.value)],
+                "global_mask": int(g.value)}
+
     def nb_width(self) -> int:
         """Entries of a chain's |B| histogram row (``fc_run_nb_width``): n + 1, or the largest
         pair count + 1 with ``FC_FLAG_NB_PAIRS``."""

@@ -781,6 +781,15 @@ int32_t fc_run_nb_width(const fc_run *r);
  * the last fc_run_frame_series_changes ran one staged pass (*series_staged = 1), the two-pass
  * form (0) or none yet (-1). */
 int fc_run_diag_paths(const fc_run *r, int64_t *tally_log_cap, int64_t *tally_log_wanted, int32_t *series_staged);
+/* The pass plan of the run's last k = 2 tally reduce (the tally counterpart of fc_run_kernel_name):
+ * the device's dynamic-LDS limit it was planned for (*lds_limit), the number of passes (*n_passes;
+ * 0: no reduce has run; at most 9) and, for the first min(*n_passes, cap) of them, the arrays each
+ * kept in LDS (lds_masks[i], bit a = array a in the order cut_hist, nb_hist, cut_times, num_flips,
+ * part_sum, last_flipped, flip_count, occupancy, last_accept) and the LDS bytes it asked for
+ * (lds_bytes[i]); *global_mask: the arrays applied with global atomics -- those above the limit
+ * and those of a pass the device refused (that pass then reads mask 0, 0 bytes). */
+int fc_run_tally_plan(const fc_run *r, int64_t *lds_limit, int32_t *n_passes, uint32_t *lds_masks, int64_t *lds_bytes,
+                      int32_t cap, uint32_t *global_mask);
 void fc_run_destroy(fc_run *r);
 
 int fc_device_count(int32_t *n);
