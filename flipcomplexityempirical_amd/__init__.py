@@ -12,6 +12,7 @@ Layers:
   chain        gerrychain-shaped drop-in API (Partition, MarkovChain, Validator, ...)
   distributed  chain sharding over GPUs + RCCL reduction of statistics
   tempering    replica exchange between the chains of one run (ladders, per-rung statistics)
+  optimization short bursts: gerrychain-shaped SingleMetricOptimizer over ReCom runs, scored and rewound on the device
 """
 from .graphs import GraphSpec  # noqa: F401
 

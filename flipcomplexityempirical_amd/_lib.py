@@ -32,6 +32,8 @@ FC_FLAG_TALLY_LOG_SMALL = 0x4  # a 64-entry tally log: the overflow path's atomi
 FC_FLAG_NB_PAIRS = 0x8  # k > 2: |b_nodes| counts the pair updater's (node, district) pairs (:151-153)
 FC_FLAG_VOTES_GLOBAL_CUR = 0x10  # fc_run_election_series: current assignment in a global row (cross-check)
 FC_HEAT_LDS_ROWS = 0x1  # fc_run_heat_series: the requested arrays privatised in LDS when they fit (cross-check)
+FC_BURST_COUNT, FC_BURST_GAP, FC_BURST_CUT = 0, 1, 2  # fc_burst_metric.kind
+FC_BURST_REWIND = 0x1  # fc_run_burst_select: restart every chain of the range from its best plan (ReCom runs)
 FC_ACCEPT_CUT, FC_ACCEPT_UNIFORM, FC_ACCEPT_ANNEAL = 0, 1, 2
 FC_LADDER_HIST = 0x1  # fc_run_set_ladders: per-rung |cut| / |B| histograms
 FC_CON_CONTIG, FC_CON_POP, FC_CON_BOUNDARY, FC_CON_FIXED, FC_CON_EMPTY = 0x1, 0x2, 0x4, 0x8, 0x100
@@ -54,6 +56,7 @@ EXPORTED = [
     "fc_run_set_localities", "fc_run_split_series", "fc_splits_eval",
     "fc_run_sample_plans", "fc_run_sample_plans_ms",
     "fc_run_heat_series", "fc_run_heat_series_info", "fc_graph_heat_rows",
+    "fc_burst_metric_init", "fc_burst_eval", "fc_run_burst_select", "fc_run_burst_select_ms",
     "fc_run_destroy",
     "fc_device_count", "fc_device_pci_id", "fc_last_error", "fc_build_flags", "fc_build_id",
 ]
@@ -103,6 +106,12 @@ class SeedParams(ctypes.Structure):
 class SeedStats(ctypes.Structure):
     _fields_ = [("attempts", ctypes.c_int64), ("trees", ctypes.c_int64), ("restarts", ctypes.c_int32),
                 ("ok", ctypes.c_int32), ("cut", ctypes.c_int32), ("nb", ctypes.c_int32)]
+
+
+class BurstMetric(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("kind", ctypes.c_int32), ("col_a", ctypes.c_int32),
+                ("col_b", ctypes.c_int32), ("num", ctypes.c_int64), ("den", ctypes.c_int64),
+                ("maximize", ctypes.c_int32)]
 
 
 class ChainStats(ctypes.Structure):
@@ -274,6 +283,10 @@ def load(build_if_missing: bool = True, allow_variant: bool = False):
     L.fc_run_heat_series.argtypes = [vp, i32, i32, u32] + [_P(i64)] * 6
     L.fc_run_heat_series_info.argtypes = [vp, _P(i32), _P(i64), _P(ctypes.c_float)]
     L.fc_graph_heat_rows.argtypes = [vp, _P(i32), _P(i32), _P(i32)]
+    L.fc_burst_metric_init.argtypes = [_P(BurstMetric), u32]
+    L.fc_burst_eval.argtypes = [_P(BurstMetric), i32, _P(i64), _P(i64), i64, _P(i64)]
+    L.fc_run_burst_select.argtypes = [vp, i32, i32, _P(BurstMetric), u32] + [_P(i64)] * 6 + [_P(ctypes.c_int8)]
+    L.fc_run_burst_select_ms.argtypes = [vp, _P(ctypes.c_float)]
     L.fc_device_pci_id.argtypes = [i32, ctypes.c_char_p, i32]
     L.fc_run_destroy.argtypes = [vp]
     L.fc_run_destroy.restype = None

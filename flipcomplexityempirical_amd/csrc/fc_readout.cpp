@@ -589,6 +589,7 @@ int fc_run_set_elections(fc_run *r, int32_t n_cols, const int32_t *node_cols, in
     if (int rc = check_hist_edges("fc_run_set_elections", "gap_edges", n_gap_edges, fc::kVoteMaxEdges, gap_edges))
         return rc;
     const int32_t n = r->g.n;
+    int64_t col_total[fc::kVoteMaxCols] = {0};
     for (int32_t j = 0; j < n_cols; ++j) {
         int64_t tot = 0;
         for (int32_t u = 0; u < n; ++u) {
@@ -599,6 +600,7 @@ int fc_run_set_elections(fc_run *r, int32_t n_cols, const int32_t *node_cols, in
         }
         if (tot > INT32_MAX)
             return fail(FC_ERR_ARG, "fc_run_set_elections: column " + std::to_string(j) + " totals over 2^31 - 1");
+        col_total[j] = tot;
     }
     for (int32_t e = 0; e < n_elections; ++e)
         if (col_a[e] < 0 || col_a[e] >= n_cols || col_b[e] < 0 || col_b[e] >= n_cols || col_a[e] == col_b[e])
@@ -617,6 +619,7 @@ int fc_run_set_elections(fc_run *r, int32_t n_cols, const int32_t *node_cols, in
         r->el_col_a[e] = e < n_elections ? col_a[e] : 0;
         r->el_col_b[e] = e < n_elections ? col_b[e] : 0;
     }
+    std::copy(col_total, col_total + fc::kVoteMaxCols, r->el_col_total);
     r->el_n_el = n_elections;
     r->el_n_edges = n_gap_edges;
     r->el_n_cols = n_cols;
@@ -1040,6 +1043,147 @@ int fc_run_heat_series_info(fc_run *r, int32_t *form, int64_t *lds_bytes, float 
     if (form) *form = r->ht_form;
     if (lds_bytes) *lds_bytes = r->ht_lds;
     return kernel_ms ? r->ht_ev.elapsed(0, 1, kernel_ms) : FC_OK;
+}
+
+// ---- short bursts (fc_burst.h, fc_burst.hip) ------------------------------------
+
+int fc_burst_metric_init(fc_burst_metric *m, uint32_t struct_size) {
+    if (!m) return fail(FC_ERR_ARG, "fc_burst_metric_init: null metric");
+    if (struct_size != sizeof(fc_burst_metric))
+        return fail(FC_ERR_ARG, "fc_burst_metric_init: struct_size is not sizeof(fc_burst_metric)");
+    std::memset(m, 0, sizeof *m);
+    m->struct_size = struct_size;
+    m->kind = FC_BURST_CUT;
+    m->num = 1;
+    m->den = 2;
+    m->maximize = 1;
+    return FC_OK;
+}
+
+int fc_burst_eval(const fc_burst_metric *m, int32_t k, const int64_t *a, const int64_t *b, int64_t cut,
+                  int64_t *score) {
+    if (!m || !score) return fail(FC_ERR_ARG, "fc_burst_eval: null argument");
+    if (const char *bad = fc::burst_metric_error(*m, 0, nullptr)) return fail(FC_ERR_ARG, std::string("fc_burst_eval: ") + bad);
+    if (k < 1 || k > fc::kMaxKGeneral) return fail(FC_ERR_ARG, "fc_burst_eval: k must be 1..32");
+    if (cut < 0) return fail(FC_ERR_ARG, "fc_burst_eval: negative cut");
+    int64_t cnt = 0, gsum = 0;
+    if (fc::burst_votes_kind(m->kind)) {
+        if (!a || !b) return fail(FC_ERR_ARG, "fc_burst_eval: null tallies");
+        int64_t total = 0;
+        for (int32_t d = 0; d < k; ++d) {
+            // (each term below 2^62 and the bound checked as the sum grows: no overflow on the way)
+            if (a[d] < 0 || b[d] < 0) return fail(FC_ERR_ARG, "fc_burst_eval: negative tally");
+            for (int64_t x : {a[d], b[d]}) {
+                if (x >= fc::kBurstProductBound || !fc::burst_product_ok(m->den, total += x))
+                    return fail(FC_ERR_ARG, "fc_burst_eval: den * (the tallies' total) reaches 2^62");
+            }
+        }
+        for (int32_t d = 0; d < k; ++d) {
+            int32_t c;
+            int64_t g;
+            fc::burst_district(a[d], b[d], m->num, m->den, c, g);
+            cnt += c;
+            gsum += g;
+        }
+    }
+    *score = fc::burst_score(m->kind, cnt, gsum, cut);
+    return FC_OK;
+}
+
+int fc_run_burst_select(fc_run *r, int32_t c0, int32_t nc, const fc_burst_metric *metric, uint32_t flags,
+                        int64_t *best_score, int64_t *best_t, int64_t *start_score, int64_t *end_score,
+                        int64_t *best_cut, int64_t *best_nb, int8_t *best_plan) {
+    const char *const who = "fc_run_burst_select";
+    if (!r || !metric) return fail(FC_ERR_ARG, "fc_run_burst_select: null argument");
+    if (const char *bad = fc::burst_metric_error(*metric, 0, nullptr))
+        return fail(FC_ERR_ARG, std::string("fc_run_burst_select: ") + bad);
+    if (flags & ~(uint32_t)FC_BURST_REWIND) return fail(FC_ERR_ARG, "fc_run_burst_select: unknown flags");
+    const bool votes = fc::burst_votes_kind(metric->kind), rewind = (flags & FC_BURST_REWIND) != 0;
+    CallRules rules;
+    rules.log_pass = "short bursts";
+    rules.unset = votes && !r->el_n_cols ? "fc_run_set_elections" : nullptr;
+    if (int rc = check_series_call(r, who, c0, nc, rules)) return rc;
+    if (const char *bad = fc::burst_metric_error(*metric, r->el_n_cols, r->el_col_total))
+        return fail(FC_ERR_ARG, std::string("fc_run_burst_select: ") + bad);
+    if (rewind && r->p.proposal != FC_PROPOSE_RECOM)
+        return fail(FC_ERR_UNSUPPORTED,
+                    "fc_run_burst_select: FC_BURST_REWIND restarts ReCom chains only: a flip chain keeps derived "
+                    "per-node state (foreign-neighbour counts, district tables, the current wait) that a rewind "
+                    "would have to rebuild on the device");
+    if (!fc::burst_fits_lds(r->npad))
+        return fail(FC_ERR_UNSUPPORTED, "fc_run_burst_select: a chain's image (" +
+                                            std::to_string(fc::burst_lds_bytes(r->npad)) +
+                                            " bytes: assignment, tallies) does not fit 48 KB of LDS");
+    if (nc == 0) return FC_OK;
+    SeriesCall s;
+    if (int rc = open_window(r, who, c0, nc, true, s)) return rc;
+    const size_t cn = (size_t)nc, npad = (size_t)r->npad, n = (size_t)r->g.n;
+    int q;
+    // the staged rows (kept by the run, shared with the plan samples) and, when the rows have
+    // padding, the same rows packed to n bytes behind them
+    const size_t want = best_plan ? cn * npad : 0;
+    const size_t held = want + (best_plan && npad != n ? cn * n : 0);
+    if (held > r->d_pl_rows.capacity()) {
+        bool fits = false;
+        if ((q = fits_free_tenth(held, fits))) return q;
+        if (!fits)
+            return fail(FC_ERR_ARG, "fc_run_burst_select: " + std::to_string(held) + " bytes of staged plans (" +
+                                        std::to_string(nc) + " chains) exceed a tenth of the free device memory; "
+                                        "split the call by chains");
+        if ((q = r->d_pl_rows.grow(held))) return q;
+    }
+    OutPack out;
+    if ((q = out.reserve(r, {cn, cn, cn, cn, cn, cn}))) return q;
+    fc::BurstParams bp{};
+    bp.log = s.log;
+    bp.cut0 = s.cut0;
+    bp.nb0 = s.nb0;
+    bp.kind = metric->kind;
+    bp.maximize = metric->maximize;
+    bp.num = metric->num;
+    bp.den = metric->den;
+    if (votes) {
+        bp.cols = r->d_el_cols;
+        bp.ncp = fc::votes_padded_cols(r->el_n_cols);
+        bp.col_a = metric->col_a;
+        bp.col_b = metric->col_b;
+    }
+    bp.rewind = rewind ? 1 : 0;
+    bp.best_score = out.at(0);
+    bp.best_t = out.at(1);
+    bp.start_score = out.at(2);
+    bp.end_score = out.at(3);
+    bp.best_cut = out.at(4);
+    bp.best_nb = out.at(5);
+    bp.best_plan = best_plan ? r->d_pl_rows.get() : nullptr;
+    if (rewind) {
+        bp.assign = r->d_assign;
+        bp.ser_a0 = r->d_ser_a0;
+        bp.sc = r->d_sc;
+    }
+    r->bs_timed = false;
+    if ((q = r->bs_ev.mark(0, r->stream))) return q;
+    const int e = fc::launch_burst(bp, r->stream);
+    if (e) return fail(FC_ERR_HIP, std::string("short bursts: ") + hipGetErrorString((hipError_t)e));
+    if ((q = r->bs_ev.mark(1, r->stream))) return q;
+    if (best_plan) {  // packed to n bytes on the device, then one contiguous copy (fc_run_sample_plans)
+        const int8_t *src = r->d_pl_rows;
+        if (npad != n) {
+            int8_t *packed = r->d_pl_rows + want;
+            HIP_TRY(hipMemcpy2DAsync(packed, n, src, npad, n, cn, hipMemcpyDeviceToDevice, r->stream));
+            src = packed;
+        }
+        HIP_TRY(hipMemcpyAsync(best_plan, src, cn * n, hipMemcpyDeviceToHost, r->stream));
+    }
+    if (int rc = out.fetch(r, {best_score, best_t, start_score, end_score, best_cut, best_nb})) return rc;
+    r->bs_timed = true;
+    return FC_OK;
+}
+
+int fc_run_burst_select_ms(fc_run *r, float *kernel_ms) {
+    if (!r || !kernel_ms) return fail(FC_ERR_ARG, "fc_run_burst_select_ms: null argument");
+    if (!r->bs_timed) return fail(FC_ERR_ARG, "fc_run_burst_select_ms: no fc_run_burst_select call recorded");
+    return r->bs_ev.elapsed(0, 1, kernel_ms);
 }
 
 int fc_graph_heat_rows(const fc_graph *g, int32_t *width, int32_t *nbr, int32_t *eid) {

@@ -8,6 +8,7 @@
 #include <utility>
 #include <vector>
 
+#include "fc_burst.h"
 #include "fc_heat.h"
 #include "fc_internal.h"
 #include "fc_ladder.h"
@@ -192,6 +193,7 @@ struct fc_run : fc::RunShape {
     // election series (fc_run_set_elections; fc_votes.h, fc_votes.hip).  el_n_cols 0: not set
     int32_t el_n_cols = 0, el_n_el = 0, el_n_edges = 0;
     int32_t el_col_a[fc::kVoteMaxElections] = {0}, el_col_b[fc::kVoteMaxElections] = {0};
+    int64_t el_col_total[fc::kVoteMaxCols] = {0};  // the columns' sums (fc_run_burst_select's overflow bound)
     DevBuf<int32_t> d_el_cols;    // [n * votes_padded_cols(el_n_cols)]
     DevBuf<int64_t> d_el_edges;   // [el_n_edges]
     DevBuf<int8_t> d_el_cur;      // per call: current-assignment rows when they are not kept in LDS
@@ -217,6 +219,10 @@ struct fc_run : fc::RunShape {
     fc::EventMarks<2> ht_ev;      // last call: before the kernel, after it
     int32_t ht_form = -1;         // last call that launched: fc::kHeatFormLds / kHeatFormGlobal (-1: none yet)
     int64_t ht_lds = 0;           // ... and the dynamic LDS bytes of its workgroups
+    // short bursts (fc_run_burst_select; fc_burst.h, fc_burst.hip): no setter (the vote columns are the
+    // election series'); the staged best-plan rows share d_pl_rows
+    fc::EventMarks<2> bs_ev;      // last call: before the kernel, after it
+    bool bs_timed = false;        // (fc_run_burst_select_ms)
     char kname[96] = {0};       // last launched flip-kernel instance
     // replica exchange (fc_run_set_ladders; fc_ladder.h, fc_exchange.hip).  Slots are flat: ladder
     // l's rung r is slot lad_off[l] + r

@@ -57,6 +57,45 @@ def sample_times(t0: int, t_last: int, every: int, first: Optional[int] = None) 
     return np.arange(start, int(t_last) + 1, int(every), dtype=np.int64)
 
 
+BURST_KINDS = {"count": _lib.FC_BURST_COUNT, "gap": _lib.FC_BURST_GAP, "cut": _lib.FC_BURST_CUT}
+
+
+@dataclass(frozen=True)
+class BurstMetric:
+    """A short-bursts metric (``fc_burst_metric``; include/flipchain.h): ``kind`` "count" (the
+    districts with ``den * a > num * (a + b)``), "gap" (|efficiency gap| in doubled integer units)
+    or "cut" (|cut|); ``col_a`` / ``col_b`` columns of :meth:`FlipRun.set_elections` (vote kinds)."""
+    kind: str = "cut"
+    col_a: int = 0
+    col_b: int = 1
+    num: int = 1
+    den: int = 2
+    maximize: bool = True
+
+    def struct(self) -> "_lib.BurstMetric":
+        m = _lib.BurstMetric()
+        check(_lib.load().fc_burst_metric_init(ctypes.byref(m), ctypes.sizeof(_lib.BurstMetric)), "fc_burst_metric_init")
+        kind = BURST_KINDS.get(self.kind, self.kind)
+        if not isinstance(kind, int):
+            raise ValueError(f"unknown metric kind {self.kind!r} (known: {', '.join(BURST_KINDS)})")
+        _set_fields(m, kind=kind, col_a=int(self.col_a), col_b=int(self.col_b), num=int(self.num), den=int(self.den),
+                    maximize=int(self.maximize))
+        return m
+
+    def eval(self, a=None, b=None, cut: int = 0) -> int:
+        """The score of one state by the rule the device applies (``fc_burst_eval``; no GPU):
+        ``a`` / ``b`` ``[k]`` the districts' tallies of the two columns, ``cut`` its |cut|."""
+        a = None if a is None else np.ascontiguousarray(a, dtype=np.int64)
+        b = None if b is None else np.ascontiguousarray(b, dtype=np.int64)
+        if (a is None) != (b is None) or (a is not None and (a.ndim != 1 or a.shape != b.shape)):
+            raise ValueError("a and b must be two [k] arrays")
+        k = 1 if a is None else int(a.size)
+        m, score = self.struct(), ctypes.c_int64(0)
+        check(_lib.load().fc_burst_eval(ctypes.byref(m), k, _p(a, ctypes.c_int64), _p(b, ctypes.c_int64), int(cut),
+                                        ctypes.byref(score)), "fc_burst_eval")
+        return int(score.value)
+
+
 class FlipGraph:
     """Native graph handle (``fc_graph_create``)."""
 
@@ -829,6 +868,37 @@ class FlipRun:
         check(_lib.load().fc_run_heat_series_info(self.handle, ctypes.byref(form), ctypes.byref(lds), ctypes.byref(ms)),
               "fc_run_heat_series_info")
         return {"form": "lds" if form.value == 0 else "global_rows", "lds_bytes": int(lds.value), "ms": float(ms.value)}
+
+    # ---- short bursts --------------------------------------------------
+    BURST_OUTPUTS = ("best_score", "best_t", "start_score", "end_score", "best_cut", "best_nb")
+
+    def burst_select(self, metric: "BurstMetric", rewind: bool = False, c0: int = 0, nc: Optional[int] = None,
+                     plans: bool = False) -> Dict[str, np.ndarray]:
+        """Scores every yield of the series window of chains ``c0 .. c0 + nc - 1`` by ``metric`` on
+        the device (``fc_run_burst_select``; include/flipchain.h): ``best_score`` and ``best_t`` (the
+        latest yield with the best score), ``start_score`` / ``end_score`` (at ``series_t0`` and at
+        ``steps``), ``best_cut`` / ``best_nb`` (|cut| and |B| at ``best_t``), int64 ``[nc]`` each, and
+        with ``plans`` ``best_plan`` int8 ``[nc, n]``, the assignment at ``best_t``.  ``rewind``
+        (ReCom runs only) restarts every chain of the range from its best plan: its state, cut / nb
+        and a fresh series window there; the draw counter, ``steps`` and the sums continue.  The vote
+        kinds read the columns of :meth:`set_elections`."""
+        nc = self.n_chains - c0 if nc is None else int(nc)
+        rows = max(nc, 0)
+        out = {key: np.zeros(rows, dtype=np.int64) for key in self.BURST_OUTPUTS}
+        if plans:
+            out["best_plan"] = np.zeros((rows, self.graph.n), dtype=np.int8)
+        m = metric.struct()
+        check(_lib.load().fc_run_burst_select(self.handle, int(c0), nc, ctypes.byref(m),
+                                              _lib.FC_BURST_REWIND if rewind else 0,
+                                              *(_p(out[key], ctypes.c_int64) for key in self.BURST_OUTPUTS),
+                                              _p(out.get("best_plan"), ctypes.c_int8)), "fc_run_burst_select")
+        return out
+
+    def burst_select_ms(self) -> float:
+        """Device ms of the last :meth:`burst_select` call's kernel (``fc_run_burst_select_ms``)."""
+        ms = ctypes.c_float(0)
+        check(_lib.load().fc_run_burst_select_ms(self.handle, ctypes.byref(ms)), "fc_run_burst_select_ms")
+        return float(ms.value)
 
     # ---- replica exchange (DESIGN.md "Replica exchange") ------------------------------
     def set_ladders(self, ladders: Sequence[Sequence[int]], hist: bool = False) -> "FlipRun":

@@ -691,6 +691,68 @@ int fc_run_heat_series_info(fc_run *r, int32_t *form, int64_t *lds_bytes, float 
  * (fc_graph_edges order) of the edge to it, -1 / -1 when empty.  nbr and eid may be NULL (width
  * only).  Pure host function; FC_ERR_UNSUPPORTED for a node degree above 16. */
 int fc_graph_heat_rows(const fc_graph *g, int32_t *width, int32_t *nbr, int32_t *eid);
+/* ---- short bursts: the score of every yield of the series window, the best of them, and the
+ * restart of a ReCom chain from the plan it held there (gerrychain's
+ * SingleMetricOptimizer.short_bursts: run b steps, keep the best plan the burst visited, ties to
+ * the latest, restart from it), by a device replay of the event log.
+ * A metric maps the state at one yield to an int64 score; a_d, b_d are district d's tallies of the
+ * vote columns col_a, col_b of fc_run_set_elections:
+ *   FC_BURST_COUNT  the districts with den * a_d > num * (a_d + b_d): with num / den = 1 / 2 the
+ *                   seats of A exactly as fc_election_eval counts them (a tie is no win), with
+ *                   another fraction the districts above a share; equality is not counted;
+ *   FC_BURST_GAP    |sum_d g(a_d, b_d)|, g as in the election series, in its doubled integer units;
+ *   FC_BURST_CUT    |cut| of the yield, from the event fields: it needs no columns.
+ * maximize = 1 looks for the largest score, 0 for the smallest.  The best yield of a window
+ * series_t0 .. steps is the LATEST yield whose score is best; the window-start state is a candidate,
+ * and a yield made by a rejected step (no event) is a yield of the state before it, so a chain
+ * whose last state has the best score has best_t = steps.                                         */
+#define FC_BURST_COUNT 0
+#define FC_BURST_GAP 1
+#define FC_BURST_CUT 2
+typedef struct fc_burst_metric {
+    uint32_t struct_size;      /* sizeof(fc_burst_metric) as the caller compiled it (fc_burst_metric_init) */
+    int32_t kind;              /* FC_BURST_*                                                */
+    int32_t col_a, col_b;      /* vote kinds: two different columns of fc_run_set_elections */
+    int64_t num, den;          /* FC_BURST_COUNT's share, 0 < num < den <= 2^20             */
+    int32_t maximize;          /* 1: the largest score is best, 0: the smallest             */
+} fc_burst_metric;
+/* Zeroes *m and sets struct_size, kind = FC_BURST_CUT, num / den = 1 / 2, maximize = 1. */
+int fc_burst_metric_init(fc_burst_metric *m, uint32_t struct_size);
+/* The score of one state by the rule the device applies: a, b [k] the districts' tallies of the
+ * metric's two columns (vote kinds; may be NULL for FC_BURST_CUT), cut its |cut|.  FC_ERR_ARG for
+ * an unknown kind, num / den outside 0 < num < den <= 2^20, maximize other than 0 / 1, k outside
+ * 1..32, a negative tally or cut, or den * (the sum of all the tallies) at 2^62 or above (a product
+ * could overflow).  The columns are not read.  Pure host function. */
+int fc_burst_eval(const fc_burst_metric *m, int32_t k, const int64_t *a, const int64_t *b, int64_t cut,
+                  int64_t *score);
+/* Scores every yield of the window of chains c0 .. c0 + nc - 1.  Per chain of the call, all int64:
+ *   best_score, best_t     the best score and the absolute index of the latest yield that has it;
+ *   start_score, end_score the scores at series_t0 and at steps;
+ *   best_cut, best_nb      |cut| and |B| at best_t;
+ *   best_plan [nc * n]     the assignment at best_t (int8, as fc_run_read_state reports it).
+ * Any output may be NULL.  Without flags nothing in the run changes: flip runs of any k and ReCom
+ * runs with a move log, with FC_DIAG_SERIES.  With FC_BURST_REWIND (ReCom runs only:
+ * FC_ERR_UNSUPPORTED for a flip run, whose derived per-node state a rewind would have to rebuild)
+ * every chain of the range restarts from its best plan, written by the kernel on the device:
+ * its assignment := the plan at best_t, its cut / nb := those of best_t, and its series window
+ * restarts there exactly as fc_run_series_reset leaves it (events = 0, series_t0 = steps,
+ * series_cut0 / series_nb0 = cut / nb, window-start plan = the plan).  draws, steps, every counter
+ * and sum, and every chain outside the range are untouched: the draw counter continues, so a chain
+ * whose best is its start plan does not repeat its burst, and the streaming sums (sum_cut, ...)
+ * cover the abandoned yields too.
+ * Checked before any device work (a refused call changes nothing): FC_ERR_ARG for a bad metric
+ * (as fc_burst_eval; columns >= n_cols or equal; den * the two columns' totals at 2^62 or above),
+ * unknown flags, a vote kind before fc_run_set_elections, a bad chain range, a window of 2^30
+ * yields or more, a chain whose log overflowed event_cap; FC_ERR_UNSUPPORTED for ReCom runs
+ * without a move log and for a chain image (n rounded up to 16, + 256 bytes) above 48 KB of LDS. */
+#define FC_BURST_REWIND 0x1u     /* restart every chain of the range from its best plan (ReCom runs) */
+int fc_run_burst_select(fc_run *r, int32_t c0, int32_t nc, const fc_burst_metric *metric, uint32_t flags,
+                        int64_t *best_score, int64_t *best_t, int64_t *start_score, int64_t *end_score,
+                        int64_t *best_cut, int64_t *best_nb,       /* [nc] each  */
+                        int8_t *best_plan);                        /* [nc * n]   */
+/* Device time of the last fc_run_burst_select call's kernel (HIP events on the run's stream).
+ * FC_ERR_ARG before the first such call. */
+int fc_run_burst_select_ms(fc_run *r, float *kernel_ms);
 /* Page-lock (pin) a caller's host buffer for faster device-to-host copies of the readers above
  * (hipHostRegister); unregister before freeing it. */
 int fc_host_register(void *ptr, int64_t bytes);
