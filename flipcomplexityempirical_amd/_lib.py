@@ -48,7 +48,7 @@ EXPORTED = [
     "fc_run_read_events", "fc_run_series_reset", "fc_run_autocorr",
     "fc_run_frame_series", "fc_run_frame_series_changes", "fc_host_register", "fc_host_unregister",
     "fc_run_kernel_name", "fc_run_n_chains", "fc_run_chain_lds_bytes", "fc_run_nb_width", "fc_run_diag_paths",
-    "fc_run_tally_plan",
+    "fc_run_tally_plan", "fc_run_ring_table",
     "fc_run_set_ladders", "fc_run_exchange", "fc_run_read_rungs", "fc_run_read_bases", "fc_run_read_rung_stats",
     "fc_ladder_swap_threshold",
     "fc_run_set_elections", "fc_run_election_series", "fc_election_eval",
@@ -93,7 +93,8 @@ class Params(ctypes.Structure):
                 # per-chain configuration
                 ("chain_pop_bounds", _P(ctypes.c_int64)),
                 # k = 2 node stream: FC_STREAM_NODE / FC_STREAM_BAND
-                ("stream", ctypes.c_int32), ("tune_multi_flip", ctypes.c_int32)]
+                ("stream", ctypes.c_int32), ("tune_multi_flip", ctypes.c_int32),
+                ("tune_ring_table", ctypes.c_int32)]
 
 
 class SeedParams(ctypes.Structure):
@@ -261,6 +262,7 @@ def load(build_if_missing: bool = True, allow_variant: bool = False):
     L.fc_run_chain_lds_bytes.restype = i32
     L.fc_run_diag_paths.argtypes = [vp, _P(i64), _P(i64), _P(i32)]
     L.fc_run_tally_plan.argtypes = [vp, _P(i64), _P(i32), _P(u32), _P(i64), i32, _P(u32)]
+    L.fc_run_ring_table.argtypes = [vp, _P(i32), _P(i32)]
     L.fc_run_nb_width.argtypes = [vp]
     L.fc_run_nb_width.restype = i32
     L.fc_run_set_ladders.argtypes = [vp, i32, _P(i32), _P(i32), u32]

@@ -242,6 +242,7 @@ int fc_params_init(fc_params *p, uint32_t struct_size) {
     p->pop_hi = INT32_MAX;
     p->hit_lo = 1;  // hitting-time window off (hit_lo > hit_hi)
     p->hit_hi = 0;
+    p->tune_ring_table = 64;  // (0 is "no table")
     return FC_OK;
 }
 
@@ -256,6 +257,13 @@ int fc_run_diag_paths(const fc_run *r, int64_t *tally_log_cap, int64_t *tally_lo
     *tally_log_cap = r->tl_cap();
     *tally_log_wanted = r->tl_want;
     *series_staged = r->series_staged;
+    return FC_OK;
+}
+
+int fc_run_ring_table(const fc_run *r, int32_t *classes, int32_t *in_use) {
+    if (!r || !classes || !in_use) return fail(FC_ERR_ARG, "fc_run_ring_table: null argument");
+    *classes = r->ring_classes;
+    *in_use = r->ring_table_on ? 1 : 0;
     return FC_OK;
 }
 
@@ -312,6 +320,7 @@ int fc_run_create(const fc_graph *gr, const fc_params *p, int32_t n_chains, cons
         fc::philox_round_keys((uint32_t)p->seed, (uint32_t)(p->seed >> 32), keys);
         if ((rc = r->d_pkeys.upload(keys, fc::kPhiloxKeyWords))) return rc;
     }
+    if ((rc = r->d_ring_table.upload(plan.ring_table))) return rc;  // (none: the buffer stays null)
     if ((rc = r->d_labels.upload(r->labels))) return rc;
     if ((rc = r->d_cut_hist.upload(plan.cut_hist))) return rc;
     if ((rc = r->d_nb_hist.upload(plan.nb_hist))) return rc;
@@ -437,7 +446,8 @@ static fc::KParams flip_params(const fc_run *r, int64_t n_steps, int64_t max_dra
     k.log1mp = r->d_log1mp;
     k.labels = r->d_labels;
     k.diag = r->p.diag_mask;
-    k.flags = (r->p.flags & ~fc::kFlagNbr4) | (r->nbr4 ? fc::kFlagNbr4 : 0u);
+    k.flags = (r->p.flags & ~(fc::kFlagNbr4 | fc::kFlagRingTable)) | (r->nbr4 ? fc::kFlagNbr4 : 0u) |
+              (r->ring_table_on ? fc::kFlagRingTable : 0u);
     k.cut_hist = r->d_cut_hist;
     k.nb_hist = r->d_nb_hist;
     k.nb_w = r->nb_w;
@@ -644,7 +654,7 @@ int fc_run_steps(fc_run *r, int64_t n_steps, int64_t max_draws, void *hip_stream
             k.eta_parity = (int32_t)(r->n_flip_launches++ & 1);
             HIP_TRY(hipMemsetAsync(r->d_eta + k.eta_parity, 0, sizeof(uint32_t), s));
         }
-        const int e = r->p.k == 2 ? fc::launch_flip2(k, r->d_pkeys, inst.flip2, s, r->kname, sizeof r->kname)
+        const int e = r->p.k == 2 ? fc::launch_flip2(k, r->d_pkeys, r->d_ring_table, inst.flip2, s, r->kname, sizeof r->kname)
                                     : fc::launch_flipk(k, inst.flipk, s, r->kname, sizeof r->kname);
         if (e != 0) return fail(FC_ERR_HIP, std::string("flip kernel launch: ") + hipGetErrorString((hipError_t)e));
         if (k.tl_len) {  // the launch's logged tallies, applied and the logs emptied

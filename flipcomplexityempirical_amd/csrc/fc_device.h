@@ -653,7 +653,8 @@ constexpr uint32_t ST_IP = 8u;   // invalid: population
 constexpr uint32_t ST_BD = 16u;  // contiguity resolved by BFS
 constexpr uint32_t ST_BR = 32u;  // ... and its result
 // per-slot predicates of the k = 2 kernel, packed beside the status bits
-constexpr uint32_t LF_HIT = 1u << 8;     // proposal (boundary node)
+constexpr uint32_t LF_HIT = 1u << 8;     // proposal (boundary node).  Read under a mask of the lanes that hold
+                                         // a slot only: flip2_kernel's table body sets it on idle lanes too
 constexpr uint32_t LF_ACC = 1u << 9;     // Metropolis test passed
 constexpr uint32_t LF_SLIN = 1u << 10;   // run rule, open ring
 constexpr uint32_t LF_SCYC = 1u << 11;   // run rule, ring closed through the outer face

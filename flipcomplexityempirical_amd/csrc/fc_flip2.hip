@@ -32,6 +32,7 @@
 #include "fc_device.h"
 #include "fc_internal.h"
 #include "fc_philox.h"
+#include "fc_ring_table.h"
 #include "fc_tally.h"
 
 namespace fc {
@@ -90,9 +91,17 @@ struct RingCells {
 // and a longer KParams would move every other kernel's hidden arguments.
 // LIST: the segment pass walks each slot's list of (at most four) neighbours instead of its ring's
 // cells; flip2_kernel chooses it per launch, for graphs without a node of more than four.
+// The LIST body also takes a slot's verdicts from the run's ring table (rtab: fc_ring_table.h, one
+// 16-bit entry per ring class and ring byte, the class in the upper half of NodeRec::deg) instead of
+// the ring arithmetic: one load for about 45 vector instructions per evaluation, in phase 2 and in
+// both re-evaluations.  A run without a table takes the other body (flip2_kernel below).
+static_assert(kReHit == LF_HIT && kReSlin == LF_SLIN && kReScyc == LF_SCYC, "a ring entry's verdict bits are st's");
 template <int RMAX, int NSUB, bool FULL, bool SEARCH, bool XTRA, bool BAND, bool LIST>
-__device__ __forceinline__ void flip2_body(const KParams &p, PhiloxKeys keys) {
+__device__ __forceinline__ void flip2_body(const KParams &p, PhiloxKeys keys, const RingEntry *__restrict__ rtab) {
     static_assert(FULL || !XTRA, "XTRA is a FULL instance");
+    // the instances that carry this body twice (flip2_kernel below)
+    constexpr bool kTwoBody = RMAX == kRingTableRmax && !FULL && !SEARCH && !BAND;
+    static_assert(!LIST || (RMAX == kRingTableRmax && !FULL && !BAND), "the ring table: lean node-stream 8-cell instances");
     // non-hit draws held per lane: the node stream's four words per Philox call, BAND's rounds
     constexpr int kRV = BAND ? NSUB : 4;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -501,7 +510,9 @@ __device__ __forceinline__ void flip2_body(const KParams &p, PhiloxKeys keys) {
         const uint64_t d = draw + (uint64_t)off_l;
         int v = has ? v_r : 0;
         uint32_t w1, w2;  // the draw's acceptance words (random(), grid_chain_sec11.py:179)
-        if constexpr (BAND) {
+        if constexpr (LIST) {
+            // (made below, between the ring table's load and its first use)
+        } else if constexpr (BAND) {
             w1 = slot[64 + lane];
             w2 = slot[128 + lane];
         } else {
@@ -527,10 +538,11 @@ __device__ __forceinline__ void flip2_body(const KParams &p, PhiloxKeys keys) {
         const NodeRec<RMAX> rec = G[v];
         int av = a[v];
         int pv = rec.pop;
-        const uint32_t Ln = (uint32_t)(rec.meta & kMetaLenMask);
-        const uint32_t full = (1u << Ln) - 1u;
+        // (ring length and links: the ring body's, unused with the table)
+        [[maybe_unused]] const uint32_t Ln = (uint32_t)(rec.meta & kMetaLenMask);
+        [[maybe_unused]] const uint32_t full = (1u << Ln) - 1u;
         uint32_t nbr = (uint32_t)(rec.meta >> kMetaNbrShift) & 0xffffu;
-        const uint32_t link = (uint32_t)(rec.meta >> kMetaLinkShift) & 0xffffu;
+        [[maybe_unused]] const uint32_t link = (uint32_t)(rec.meta >> kMetaLinkShift) & 0xffffu;
         int cell[RMAX];  // ring cells (padded with the node itself)
         // districts are 0 / 1: pack the ring's district-1 bits, then A's bits are those or
         // their complement (shift-ors, no compare / select per cell)
@@ -547,30 +559,68 @@ __device__ __forceinline__ void flip2_body(const KParams &p, PhiloxKeys keys) {
         for (int i = 0; i < RMAX; ++i) asm volatile("" : "+v"(ad[i]));
 #pragma unroll
         for (int i = 0; i < RMAX; ++i) in1 |= (uint32_t)ad[i] << i;
-        uint32_t inA = (av ? in1 : ~in1) & full;
-        slot[256 + lane] = link | (Ln << 16);  // for re-evaluations inside the commit
-        // target district: 1 - av (-1 * assignment, grid_chain_sec11.py:145)
-        const uint32_t nbrA = inA & nbr;        // old-district neighbours
-        uint32_t tmask = nbr & ~inA;            // target-district neighbours
-        int nA = __popc(nbrA);
-        int delta = nA - __popc(tmask);         // cut(S') - cut(S)
-        const bool hit = has && tmask != 0u;    // v in b_nodes: a proposal
-        bool s_lin, s_cyc;
-        {
-            const uint32_t rot = Ln ? (((inA >> 1) | (inA << (Ln - 1))) & full) : 0u;
-            const uint32_t lk = inA & rot & link;
-            s_lin = one_run_flat(nbrA, full & ~lk, full);
-            // the ring's closing step (cell Ln-1 to cell 0), when both ends are in A
-            const uint32_t vlink = (Ln >= 2) ? ((inA & (inA >> (Ln - 1)) & 1u) << (Ln - 1)) : 0u;
-            s_cyc = one_run_flat(nbrA, full & ~(lk | vlink), full);
+        uint32_t inA, tmask, st;
+        int nA, delta;
+        // LIST: the slot's row of the ring table (its node's class), kept for the re-evaluations
+        uint32_t trow = 0u;
+        if constexpr (LIST) {
+            // the verdicts from the table.  A padded cell holds the node, so inA has its bits from the
+            // ring length up to the byte's end set; every entry is that of the byte's bits below the
+            // length, and nothing after this reads inA above a neighbour's position: no length mask
+            inA = (av ? in1 : ~in1) & (kRingTableRow - 1u);
+            const bool exact = SEARCH ? (rec.meta & kMetaExact) && !force_bfs : true;
+            const bool gam = (rec.meta & kMetaGamma) != 0;
+            trow = ((uint32_t)rec.deg >> 16) << kRingTableRmax;
+            uint32_t idx = trow | inA;
+            // the load issues here and the acceptance words' Philox call runs under it (tied through
+            // the index and the entry, so that the call is neither hoisted above the load nor the
+            // entry waited for before the call)
+            uint32_t dlo = (uint32_t)d;
+            asm volatile("" : "+v"(idx), "+v"(dlo));
+            uint32_t e = rtab[idx];
+            {  // (words 1-2 of the draw's own call, as in the other body; no tape: not an XTRA instance)
+                const PhiloxKeys pk = batch_keys<FULL>(keys);
+                const Words4 g = philox4x32_10_keys(dlo, (uint32_t)(d >> 32), chain_gid, 0u, pk);
+                w1 = g.x1;
+                w2 = g.x2;
+            }
+            asm volatile("" : "+v"(e), "+v"(w1), "+v"(w2));
+            tmask = nbr & ~inA;             // target-district neighbours (the commit reads them)
+            nA = ring_entry_na(e);
+            delta = ring_entry_delta(e);
+            const bool acc = mant53(w1, w2) < T[e & kReDeltaMask];
+            // (LF_HIT without `has`: an idle lane's bit is never read, PROP ends at the last slot)
+            st = (e & kReVerdicts) | (acc ? LF_ACC : 0u) | (exact ? LF_EXACT : 0u) | (gam ? LF_GAM : 0u) |
+                 (has ? LF_HAS : 0u);
+        } else {
+            inA = (av ? in1 : ~in1) & full;
+            slot[256 + lane] = link | (Ln << 16);  // for re-evaluations inside the commit
+            // target district: 1 - av (-1 * assignment, grid_chain_sec11.py:145)
+            const uint32_t nbrA = inA & nbr;        // old-district neighbours
+            tmask = nbr & ~inA;                     // target-district neighbours
+            nA = __popc(nbrA);
+            delta = nA - __popc(tmask);             // cut(S') - cut(S)
+            const bool hit = has && tmask != 0u;    // v in b_nodes: a proposal
+            bool s_lin, s_cyc;
+            if constexpr (kTwoBody) {
+                ring_runs(inA, nbrA, link, Ln, full, s_lin, s_cyc);
+            } else {  // (the same expressions as ring_runs, written out as they have been: through the call
+               // the FULL, SEARCH, BAND and 16-cell instances compiled to other code)
+                const uint32_t rot = Ln ? (((inA >> 1) | (inA << (Ln - 1))) & full) : 0u;
+                const uint32_t lk = inA & rot & link;
+                s_lin = one_run_flat(nbrA, full & ~lk, full);
+                // the ring's closing step (cell Ln-1 to cell 0), when both ends are in A
+                const uint32_t vlink = (Ln >= 2) ? ((inA & (inA >> (Ln - 1)) & 1u) << (Ln - 1)) : 0u;
+                s_cyc = one_run_flat(nbrA, full & ~(lk | vlink), full);
+            }
+            const bool exact = SEARCH ? (rec.meta & kMetaExact) && !force_bfs : true;
+            const bool gam = (rec.meta & kMetaGamma) != 0;
+            const bool acc = mant53(w1, w2) < T[delta + RMAX];
+            // per-slot predicates live as bits of one VGPR (st) through the commit; the compiler
+            // would otherwise hold each as a 64-bit lane mask in SGPRs for the whole loop
+            st = (hit ? LF_HIT : 0u) | (acc ? LF_ACC : 0u) | (s_lin ? LF_SLIN : 0u) | (s_cyc ? LF_SCYC : 0u) |
+                 (exact ? LF_EXACT : 0u) | (gam ? LF_GAM : 0u) | (has ? LF_HAS : 0u);
         }
-        const bool exact = SEARCH ? (rec.meta & kMetaExact) && !force_bfs : true;
-        const bool gam = (rec.meta & kMetaGamma) != 0;
-        const bool acc = mant53(w1, w2) < T[delta + RMAX];
-        // per-slot predicates live as bits of one VGPR (st) through the commit; the compiler
-        // would otherwise hold each as a 64-bit lane mask in SGPRs for the whole loop
-        uint32_t st = (hit ? LF_HIT : 0u) | (acc ? LF_ACC : 0u) | (s_lin ? LF_SLIN : 0u) | (s_cyc ? LF_SCYC : 0u) |
-                      (exact ? LF_EXACT : 0u) | (gam ? LF_GAM : 0u) | (has ? LF_HAS : 0u);
         if (XTRA && (rec.meta & kMetaFrozen)) st |= LF_FRZ;
 #ifdef FC_PHASE_PROF
         bool first_it = true;
@@ -607,7 +657,7 @@ __device__ __forceinline__ void flip2_body(const KParams &p, PhiloxKeys keys) {
             // (no marks to clear: every segment pass clears its own before anything else runs)
             compiler_fence();
             if (has && lane >= from) {
-                const uint32_t lkl = slot[256 + lane];
+                const uint32_t lkl = LIST ? 0u : slot[256 + lane];
                 const uint32_t w1r = (!FULL && !BAND) ? w1 : slot[64 + lane], w2r = (!FULL && !BAND) ? w2 : slot[128 + lane];
                 if (vfx < 0) {
                     av = a[v];
@@ -625,23 +675,39 @@ __device__ __forceinline__ void flip2_body(const KParams &p, PhiloxKeys keys) {
                     av = self ? 1 - av : av;
                     inA = (self ? ~inA : inA) ^ eqx;
                 }
-                // nbr has no bits at or above the ring length: these need no length mask
-                const uint32_t nbA = inA & nbr;
-                tmask = nbr & ~inA;
-                nA = __popc(nbA);
-                delta = nA - __popc(tmask);
-                const uint64_t th = T[delta + RMAX];
-                const uint32_t lnk = lkl & 0xffffu, L2 = lkl >> 16;
-                const uint32_t fl = (1u << L2) - 1u;
-                inA &= fl;
-                const uint32_t rot = L2 ? (((inA >> 1) | (inA << (L2 - 1))) & fl) : 0u;
-                const uint32_t lk = inA & rot & lnk;
-                const bool sl = one_run_flat(nbA, fl & ~lk, fl);
-                const uint32_t vlink = (L2 >= 2) ? ((inA & (inA >> (L2 - 1)) & 1u) << (L2 - 1)) : 0u;
-                const bool sc = one_run_flat(nbA, fl & ~(lk | vlink), fl);
-                const bool ac = mant53(w1r, w2r) < th;
-                st = (st & (LF_EXACT | LF_GAM | LF_HAS | LF_FRZ)) | (tmask != 0u ? LF_HIT : 0u) | (ac ? LF_ACC : 0u) |
-                     (sl ? LF_SLIN : 0u) | (sc ? LF_SCYC : 0u);
+                if constexpr (LIST) {
+                    // the new view's entry (inA's bits at the ring length and up are the table's to ignore)
+                    inA &= kRingTableRow - 1u;
+                    const uint32_t e = rtab[trow | inA];
+                    tmask = nbr & ~inA;
+                    nA = ring_entry_na(e);
+                    delta = ring_entry_delta(e);
+                    const bool ac = mant53(w1r, w2r) < T[e & kReDeltaMask];
+                    st = (st & (LF_EXACT | LF_GAM | LF_HAS | LF_FRZ)) | (e & kReVerdicts) | (ac ? LF_ACC : 0u);
+                } else {
+                    // nbr has no bits at or above the ring length: these need no length mask
+                    const uint32_t nbA = inA & nbr;
+                    tmask = nbr & ~inA;
+                    nA = __popc(nbA);
+                    delta = nA - __popc(tmask);
+                    const uint64_t th = T[delta + RMAX];
+                    const uint32_t lnk = lkl & 0xffffu, L2 = lkl >> 16;
+                    const uint32_t fl = (1u << L2) - 1u;
+                    inA &= fl;
+                    bool sl, sc;
+                    if constexpr (kTwoBody) {
+                        ring_runs(inA, nbA, lnk, L2, fl, sl, sc);
+                    } else {
+                        const uint32_t rot = L2 ? (((inA >> 1) | (inA << (L2 - 1))) & fl) : 0u;
+                        const uint32_t lk = inA & rot & lnk;
+                        sl = one_run_flat(nbA, fl & ~lk, fl);
+                        const uint32_t vlink = (L2 >= 2) ? ((inA & (inA >> (L2 - 1)) & 1u) << (L2 - 1)) : 0u;
+                        sc = one_run_flat(nbA, fl & ~(lk | vlink), fl);
+                    }
+                    const bool ac = mant53(w1r, w2r) < th;
+                    st = (st & (LF_EXACT | LF_GAM | LF_HAS | LF_FRZ)) | (tmask != 0u ? LF_HIT : 0u) | (ac ? LF_ACC : 0u) |
+                         (sl ? LF_SLIN : 0u) | (sc ? LF_SCYC : 0u);
+                }
             }
             compiler_fence();
             FC_STAMP(t_re1);
@@ -1429,19 +1495,31 @@ __device__ __forceinline__ void flip2_body(const KParams &p, PhiloxKeys keys) {
 // of its candidates' neighbour counts) ran slower than the ring walk alone, and the list cost the
 // FULL, SEARCH and BAND instances scratch they did not have and the lean <16, ...> ones a wave per
 // SIMD (profiles/r10a_flip2_neighbours.txt): those keep the ring walk.
+// The list body reads the slot verdicts from the run's ring table (kFlagRingTable: the run has one);
+// a run without a table -- more ring classes than fc_params.tune_ring_table, or the knob at 0 --
+// takes the ring body with the arithmetic, like a graph with a node of five neighbours.  These
+// instances take the table's pointer as a third argument (not in KParams, for the keys' reason);
+// every other instance is the two-argument kernel it was, and is never launched with a table.
+template <int RMAX, bool FULL, bool SEARCH, bool BAND>
+constexpr bool kTwoBodies = RMAX == kRingTableRmax && !FULL && !SEARCH && !BAND;
 template <int RMAX, int NSUB, bool FULL, bool SEARCH, bool XTRA, bool BAND>
 __global__ __launch_bounds__(256, (RMAX == 8 ? 4 : 1)) void flip2_kernel(KParams p, PhiloxKeys keys) {
-    if constexpr (RMAX == 8 && !FULL && !SEARCH && !BAND) {
-        if (p.flags & kFlagNbr4) {
-            flip2_body<RMAX, NSUB, FULL, SEARCH, XTRA, BAND, true>(p, keys);
-            return;
-        }
+    static_assert(!kTwoBodies<RMAX, FULL, SEARCH, BAND>, "the lean node-stream 8-cell instances take the table argument");
+    flip2_body<RMAX, NSUB, FULL, SEARCH, XTRA, BAND, false>(p, keys, nullptr);
+}
+template <int RMAX, int NSUB, bool FULL, bool SEARCH, bool XTRA, bool BAND>
+__global__ __launch_bounds__(256, (RMAX == 8 ? 4 : 1)) void flip2_kernel(KParams p, PhiloxKeys keys, const RingEntry *rtab) {
+    static_assert(kTwoBodies<RMAX, FULL, SEARCH, BAND>, "only the lean node-stream 8-cell instances carry two bodies");
+    constexpr uint32_t kBoth = kFlagNbr4 | kFlagRingTable;
+    if ((p.flags & kBoth) == kBoth) {
+        flip2_body<RMAX, NSUB, FULL, SEARCH, XTRA, BAND, true>(p, keys, rtab);
+        return;
     }
-    flip2_body<RMAX, NSUB, FULL, SEARCH, XTRA, BAND, false>(p, keys);
+    flip2_body<RMAX, NSUB, FULL, SEARCH, XTRA, BAND, false>(p, keys, nullptr);
 }
 
-int launch_flip2(const KParams &p, const uint32_t *pkeys, const Flip2Instance &inst, void *stream, char *name,
-                 size_t name_cap) {
+int launch_flip2(const KParams &p, const uint32_t *pkeys, const uint16_t *ring_table, const Flip2Instance &inst,
+                 void *stream, char *name, size_t name_cap) {
     // one chain (wave) per workgroup: the dispatcher then deals consecutive chains, whose
     // bases differ, round-robin over the XCDs, CUs and SIMDs, and the short-boundary chains
     // that set the launch time spread more evenly over the SIMDs than four to a workgroup
@@ -1453,6 +1531,7 @@ int launch_flip2(const KParams &p, const uint32_t *pkeys, const Flip2Instance &i
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid(blocks), block(kWave * wpb);
     const PhiloxKeys keys = (PhiloxKeys)(uintptr_t)pkeys;  // the run's own table (fc_run_create)
+    if ((p.flags & kFlagRingTable) && !ring_table) return (int)hipErrorInvalidValue;  // (the flag promises one)
     // (FULL, XTRA) is one level -- 0 lean, 1 full, 2 full + xtra: there is no XTRA instance that is not FULL.
     // (The order of each list keeps the instances' order in the code object: fc_device.h with_value)
     const bool ok = with_value<16, 8>(inst.ring, [&](auto r) {
@@ -1466,7 +1545,15 @@ int launch_flip2(const KParams &p, const uint32_t *pkeys, const Flip2Instance &i
                         const Flip2Instance built{R, S, F, X, Y, B};  // what is launched is what is named
                         if (!(built == inst)) return false;
                         if (name) format_instance(built, name, name_cap);
-                        launch_lds(flip2_kernel<R, S, F, X, Y, B>, grid, block, lds, s, p, keys);
+                        // (two kernels of one name, told apart by their arguments: the typed pointer
+                        // picks the overload, and each overload asserts the instances it is for)
+                        if constexpr (kTwoBodies<R, F, X, B>) {
+                            void (*kern)(KParams, PhiloxKeys, const RingEntry *) = flip2_kernel<R, S, F, X, Y, B>;
+                            launch_lds(kern, grid, block, lds, s, p, keys, ring_table);
+                        } else {
+                            void (*kern)(KParams, PhiloxKeys) = flip2_kernel<R, S, F, X, Y, B>;
+                            launch_lds(kern, grid, block, lds, s, p, keys);
+                        }
                         return true;
                     });
                 });

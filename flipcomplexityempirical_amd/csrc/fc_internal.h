@@ -46,6 +46,10 @@ constexpr uint32_t kMetaPosNone = 15u;
 // KParams.flags bit 31 (no public FC_FLAG_*; fc_run_create sets it from the records): no node has
 // more than four neighbours, so the four positions name them all (flip2_kernel's LIST form)
 constexpr uint32_t kFlagNbr4 = 1u << 31;
+// KParams.flags bit 30 (set per run like kFlagNbr4, and only with it): the run has a ring-verdict
+// table (fc_ring_table.h; flip2_kernel's trailing argument) and its records carry each node's ring
+// class in the upper half of NodeRec::deg
+constexpr uint32_t kFlagRingTable = 1u << 30;
 inline uint64_t meta_nbr_positions(uint32_t nbr) {
     uint64_t pos = 0;
     for (int i = 0; i < 4; ++i) {
@@ -264,9 +268,11 @@ int launch_seed(const SeedParams &p, int ring_max, void *stream, char *name, siz
 int launch_flipk(const KParams &p, const FlipKInstance &inst, void *stream, char *name, size_t name_cap);  // k > 2 (fc_kernels.hip)
 // k = 2 (fc_flip2.hip).  pkeys: [kPhiloxKeyWords] the seed's Philox round keys (fc_philox.h), in
 // device memory; the kernel takes the pointer as an argument of its own after KParams, so the
-// struct (and with it every other kernel's argument layout) does not carry it
-int launch_flip2(const KParams &p, const uint32_t *pkeys, const Flip2Instance &inst, void *stream, char *name,
-                 size_t name_cap);
+// struct (and with it every other kernel's argument layout) does not carry it.  ring_table: the
+// run's ring-verdict table (fc_ring_table.h), the kernel's last argument for the same reason; read
+// only with kFlagRingTable in p.flags (null without)
+int launch_flip2(const KParams &p, const uint32_t *pkeys, const uint16_t *ring_table, const Flip2Instance &inst,
+                 void *stream, char *name, size_t name_cap);
 // k = 2 full diagnostics: apply every chain's tally log (KParams tl_*) to the per-chain
 // histograms / per-node / per-edge arrays and reset the logs (fc_tally.hip).  `used` (may be null)
 // receives the pass plan as launched (fc_tally_plan.h), a pass the device refused demoted in it

@@ -5,9 +5,11 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstring>
 
 #include "fc_philox.h"
+#include "fc_ring_table.h"
 
 namespace fc {
 namespace {
@@ -291,6 +293,13 @@ int plan_tune(const HostGraph &g, const fc_params *p, RunPlan &r, std::string &e
     if (t.wpb != 1 && t.wpb != 2 && t.wpb != 4)
         return bad(err, FC_ERR_ARG, "fc_run_create: tune_chains_per_block must be 1, 2 or 4");
     t.wpb = std::min(t.wpb, waves_per_block(r.chain_lds_bytes));
+    // k = 2, 8-cell rings: the ring verdicts from a table of (ring class, ring bits) when the graph
+    // has at most this many classes (fc_ring_table.h; 256 entries of 2 B per class).  0: no table
+    // (fc_params_init sets the default, 64 classes = 32 KB: the hot rows stay in the vector L1)
+    t.ring_table = p->tune_ring_table;
+    if (t.ring_table < 0 || t.ring_table > kRingTableMaxClasses)
+        return bad(err, FC_ERR_ARG, "fc_run_create: tune_ring_table must be in [0, " + std::to_string(kRingTableMaxClasses) +
+                                    "] (0: no table)");
     // large k > 2 chains that need the search: 4 = one chain per 256-thread workgroup,
     // searched by all of it.  Default 1: the workgroup's helper waves carry the kernel's
     // VGPR count, so a chain then holds four waves' registers and fewer chains are
@@ -577,6 +586,24 @@ int plan_run(const HostGraph &g, const fc_params &params, int32_t n_chains, cons
     plan.node_recs = g.ring_max == 8 ? pack_records<8>(g, p->frozen, p->n_frozen) : pack_records<16>(g, p->frozen, p->n_frozen);
     plan.nbr4 = true;
     for (uint64_t m : g.meta) plan.nbr4 = plan.nbr4 && __builtin_popcount((uint32_t)(m >> kMetaNbrShift) & 0xffffu) <= 4;
+    // k = 2 flips on 8-cell rings: the ring verdicts as a table per class of node (fc_ring_table.h).  A
+    // function of the graph alone; the records of such a run carry each node's class above its degree
+    // (only the k > 2 kernel reads the degree, and its runs get the plain records)
+    if (p->k == 2 && p->proposal != FC_PROPOSE_RECOM && g.ring_max == kRingTableRmax) {
+        std::vector<uint16_t> cls;
+        // (the kernel reads the table in its neighbour-list body only: none for a graph that takes the other)
+        plan.ring_classes = build_ring_table(g.meta.data(), g.n, plan.nbr4 ? plan.tune.ring_table : 0, cls, plan.ring_table);
+        plan.ring_table_on = !plan.ring_table.empty();
+        if (plan.ring_table_on) {
+            for (int32_t v = 0; v < g.n; ++v) {
+                unsigned char *at = plan.node_recs.data() + (size_t)v * sizeof(NodeRec<8>) + offsetof(NodeRec<8>, deg);
+                int32_t deg;
+                std::memcpy(&deg, at, sizeof deg);
+                deg |= (int32_t)cls[v] << 16;
+                std::memcpy(at, &deg, sizeof deg);
+            }
+        }
+    }
     if (p->proposal == FC_PROPOSE_RECOM) recom_tables(g, bases ? bases[0] : p->base, plan);
     // the event log (FC_DIAG_SERIES with a capacity) and the traced chains
     if ((p->diag_mask & FC_DIAG_SERIES) && p->event_cap > 0)

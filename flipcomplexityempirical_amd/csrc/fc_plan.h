@@ -24,6 +24,7 @@ constexpr uint64_t kFnvBasis = 0xcbf29ce484222325ull;
 // fc_params.tune_* with the defaults filled in
 struct RunTune {
     int32_t nsub, hit_stop, par_min, wait_q, wpb, coop, deal, multi;
+    int32_t ring_table;      // k = 2: most ring classes a lookup table is built for (0: none)
     int32_t prio_div[3];     // prio_div[0] <= 0: priorities off
     float prio_th[3];
 };
@@ -48,6 +49,8 @@ struct RunShape {
     uint64_t param_hash = 0;     // FNV-1a of every trajectory-determining parameter (checkpoint check)
     bool variant = false;        // accept / constraint variants (FULL k = 2 instance)
     bool nbr4 = false;           // no node has more than four neighbours (kFlagNbr4), from the records
+    int32_t ring_classes = 0;    // k = 2 flips, 8-cell rings: distinct (length, neighbours, links) of the nodes' rings
+    bool ring_table_on = false;  // ... and a verdict table was built for them (kFlagRingTable, fc_ring_table.h)
     RunTune tune{};
     std::vector<double> bases0;        // [n_chains] the base each chain was created with
     std::vector<int64_t> pop_bounds;   // [2 * n_chains]
@@ -55,7 +58,9 @@ struct RunShape {
 
 // The plan: the shape plus the host vectors fc_run_create uploads (an empty one: no such buffer).
 struct RunPlan : RunShape {
-    std::vector<unsigned char> node_recs;  // NodeRec<ring_max>[n], frozen nodes marked
+    std::vector<unsigned char> node_recs;  // NodeRec<ring_max>[n], frozen nodes marked; with a ring table, each
+                                           // node's class in the upper half of NodeRec::deg
+    std::vector<uint16_t> ring_table;      // [ring_classes * 256] RingEntry (fc_ring_table.h); empty: none
     std::vector<int8_t> assign;            // [n_chains * npad]
     std::vector<uint8_t> fcnt;             // [n_chains * npad]
     std::vector<ChainScalars> sc;          // [n_chains]

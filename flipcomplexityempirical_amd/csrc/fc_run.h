@@ -138,6 +138,7 @@ struct fc_run : fc::RunShape {
     DevBuf<uint64_t> d_thresh;
     DevBuf<double> d_log1mp;
     DevBuf<uint32_t> d_pkeys;  // the seed's Philox round keys (k = 2 flip kernel)
+    DevBuf<uint16_t> d_ring_table;  // [ring_classes * 256] ring verdicts by class and ring bits (k = 2; null: none)
     DevBuf<int32_t> d_labels;
     DevBuf<int64_t> d_cut_hist, d_nb_hist;
     DevBuf<int64_t> d_edge_acc;

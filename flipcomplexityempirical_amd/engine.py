@@ -246,7 +246,7 @@ class RunConfig:
     recom_max_attempts: int = 0
     # launch tuning (fc_params.tune_*): scheduling only, never the trajectory; 0 = default.
     # Keys: nsub, hit_stop, par_min, wait_queue, chains_per_block, prio_div (3), prio_th (3),
-    # search_waves, deal, multi_flip.
+    # search_waves, deal, multi_flip, ring_table (0 = no table: a value there, the default is 64).
     tune: Optional[Dict[str, object]] = None
     # k = 2 node stream (fc_params.stream): "node" draws over all n nodes, "band" over the band
     # S = b_nodes + neighbours; the chain's law is the same, the trajectory not
@@ -254,7 +254,7 @@ class RunConfig:
 
 
 TUNE_KEYS = ("nsub", "hit_stop", "par_min", "wait_queue", "chains_per_block", "prio_div", "prio_th",
-             "search_waves", "deal", "multi_flip")
+             "search_waves", "deal", "multi_flip", "ring_table")
 
 
 def parse_tune(text: str) -> Dict[str, object]:
@@ -975,6 +975,13 @@ class FlipRun:
                                             ctypes.byref(g)), "fc_run_tally_plan")
         return {"limit": int(limit.value), "passes": [(int(masks[i]), int(nbytes[i])) for i in range(n.value)],
                 "global_mask": int(g.value)}
+
+    def ring_table(self) -> Dict[str, int]:
+        """The k = 2 ring-verdict table (``fc_run_ring_table``): the classes the graph's rings fall
+        into and whether the run holds a table (1: its lean node-stream launches read it) or none (0)."""
+        classes, used = ctypes.c_int32(0), ctypes.c_int32(0)
+        check(_lib.load().fc_run_ring_table(self.handle, ctypes.byref(classes), ctypes.byref(used)), "fc_run_ring_table")
+        return {"classes": int(classes.value), "in_use": int(used.value)}
 
     def nb_width(self) -> int:
         """Entries of a chain's |B| histogram row (``fc_run_nb_width``): n + 1, or the largest

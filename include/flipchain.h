@@ -211,6 +211,17 @@ typedef struct fc_params {
                                    marks, one LDS byte per node -- on (0 / 1) takes the exact marks
                                    when they cost no residency, fc_run_kernel_name shows which).
                                    Scheduling only, like every tune_* field                    */
+    int32_t tune_ring_table;    /* k = 2, rings of at most 8 cells, graphs without a node of more
+                                   than four neighbours: the ring verdicts of a proposal are read
+                                   from a table of (ring class, ring bits), built once per run,
+                                   when the graph's rings fall into at most this many classes
+                                   (distinct length / neighbour / link masks; 512 B per class).
+                                   Unlike the other tune_* fields 0 is a value, not the default:
+                                   0 = no table (the arithmetic), fc_params_init sets 64; at most
+                                   255.  A caller that zero-fills the struct instead of calling
+                                   fc_params_init gets no table, and with it the kernel's ring body
+                                   (about a tenth slower on sec11): set 64.  Scheduling only:
+                                   both forms give the same verdicts                             */
 } fc_params;
 
 #define FC_STREAM_NODE 0
@@ -843,6 +854,14 @@ int32_t fc_run_nb_width(const fc_run *r);
  * the last fc_run_frame_series_changes ran one staged pass (*series_staged = 1), the two-pass
  * form (0) or none yet (-1). */
 int fc_run_diag_paths(const fc_run *r, int64_t *tally_log_cap, int64_t *tally_log_wanted, int32_t *series_staged);
+/* The ring-verdict table of a k = 2 flip run on rings of at most 8 cells (fc_params.tune_ring_table):
+ * the classes the graph's rings fall into (*classes; 0 for any other run) and whether the run holds
+ * a table (*in_use = 1) or none (0: more classes than the cap, the knob at 0, or a node with more
+ * than four neighbours).  A table is read by the launches of the lean node-stream instance
+ * (fc_run_kernel_name: flip2_kernel<8, *, false, false, false, false>); a run with diagnostics, the
+ * band stream or the search holds it unread and evaluates the arithmetic.  The verdicts are the
+ * same either way. */
+int fc_run_ring_table(const fc_run *r, int32_t *classes, int32_t *in_use);
 /* The pass plan of the run's last k = 2 tally reduce (the tally counterpart of fc_run_kernel_name):
  * the device's dynamic-LDS limit it was planned for (*lds_limit), the number of passes (*n_passes;
  * 0: no reduce has run; at most 9) and, for the first min(*n_passes, cap) of them, the arrays each
