@@ -25,7 +25,7 @@ LIB = os.environ.get("FC_LIB_OUT") or os.path.join(PKG, f"libflipchain_{VARIANT}
 SOURCES = ["fc_flip2.hip", "fc_deal.hip", "fc_kernels.hip", "fc_series.hip", "fc_recom.hip", "fc_seed.hip", "fc_exchange.hip",
            "fc_votes.hip", "fc_shapes.hip", "fc_splits.hip", "fc_plans.hip", "fc_heat.hip", "fc_tally.hip", "fc_burst.hip",
            "fc_capi.cpp", "fc_plan.cpp", "fc_ckpt.cpp", "fc_tempering.cpp", "fc_readout.cpp", "fc_graph.cpp"]
-HEADERS = ["fc_internal.h", "fc_instance.h", "fc_lds.h", "fc_philox.h", "fc_device.h", "fc_ring.h", "fc_ring_table.h", "fc_ladder.h", "fc_plan.h",
+HEADERS = ["fc_internal.h", "fc_instance.h", "fc_lds.h", "fc_philox.h", "fc_device.h", "fc_ring.h", "fc_ring_table.h", "fc_lane_mask.h", "fc_ladder.h", "fc_plan.h",
            "fc_run.h",           "fc_votes.h", "fc_shapes.h", "fc_splits.h", "fc_plans.h", "fc_heat.h", "fc_tally.h", "fc_tally_plan.h", "fc_replay.h",
            "fc_replay_dev.h", "fc_burst.h", "fc_recom_body.h", "fc_bipartition.h", "fc_tree_dev.h",
            os.path.join("..", "..", "include", "flipchain.h")]

@@ -31,6 +31,7 @@
 
 #include "fc_device.h"
 #include "fc_internal.h"
+#include "fc_lane_mask.h"
 #include "fc_philox.h"
 #include "fc_ring_table.h"
 #include "fc_tally.h"
@@ -70,6 +71,48 @@ __device__ __forceinline__ PhiloxKeys batch_keys(PhiloxKeys keys) {
         asm volatile("" : "+s"(keys));
         return keys;
     }
+}
+
+// Wave-uniform lane ranges.  LEAN (the three lean node-stream 8-cell instances, which carry the body
+// twice): fc_lane_mask.h's forms, shifts without a compare or a select; the other instances keep
+// fc_device.h's, and with them their code.  m_upto: the call site has the bound below 64;
+// m_range_lo_ge1 / m_after_ge1: the lower bound below 64 and the upper at least 1; m_below_ge1: n >= 1.
+template <bool LEAN>
+__device__ __forceinline__ uint64_t m_below(int n) {
+    if constexpr (LEAN) return lanes_below(n);
+    else return bits_below(n);
+}
+template <bool LEAN>
+__device__ __forceinline__ uint64_t m_below_ge1(int n) {
+    if constexpr (LEAN) return lanes_below_ge1(n);
+    else return bits_below(n);
+}
+template <bool LEAN>
+__device__ __forceinline__ uint64_t m_upto(int n) {  // lanes 0 .. n
+    if constexpr (LEAN) return lanes_upto_lt64(n);
+    else return bits_below(n + 1);
+}
+template <bool LEAN>
+__device__ __forceinline__ uint64_t m_range_lo_ge1(int lo, int hi) {  // lanes lo .. hi - 1
+    if constexpr (LEAN) return lanes_in_lo_lt64_hi_ge1(lo, hi);
+    else return lane_range(lo, hi);
+}
+template <bool LEAN>
+__device__ __forceinline__ uint64_t m_after_ge1(int lo, int hi) {  // lanes lo + 1 .. hi - 1
+    if constexpr (LEAN) return lanes_after_lt64_hi_ge1(lo, hi);
+    else return lane_range(lo + 1, hi);
+}
+// KParams once more, from the kernel-argument segment (flip2_kernel's first argument sits at its
+// start): what a rare path of the batch loop reads through this pointer -- the issue-priority block,
+// wait_flush -- is loaded there, a scalar load per word, and not held in scalar registers across
+// the loop.  The lean instances spill 75 of those; with the priority words and the seeds out of the
+// loop's live set they spill 47, and the list body's loop reloads 8 words from the spill register
+// where it reloaded 34 (profiles/r14a_flip2_scalar.txt).
+typedef const KParams __attribute__((address_space(4))) *KArgs;
+__device__ __forceinline__ KArgs kparams_again() {
+    KArgs ka = (KArgs)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(ka));
+    return ka;
 }
 
 // The cells a segment pass walks for a slot: its first four neighbours' (two ids to a register: the
@@ -317,8 +360,14 @@ __device__ __forceinline__ void flip2_body(const KParams &p, PhiloxKeys keys, co
         }
         if (want_wait && lane < qn) {  // the loads before the tallies' atomics (vmcnt completes in order)
             const uint64_t dq = q_d[lane];
-            const Words4 g = philox4x32_10((uint32_t)dq, (uint32_t)(dq >> 32), chain_gid, 1u, p.seed_lo, p.seed_hi);
-            w = geom_wait_of(g.x0, g.x1, p.log1mp[q_nb[lane]]);
+            if constexpr (kTwoBody) {  // (a rare path: the seed and the table's pointer are read again)
+                const KArgs ka = kparams_again();
+                const Words4 g = philox4x32_10((uint32_t)dq, (uint32_t)(dq >> 32), chain_gid, 1u, ka->seed_lo, ka->seed_hi);
+                w = geom_wait_of(g.x0, g.x1, ka->log1mp[q_nb[lane]]);
+            } else {
+                const Words4 g = philox4x32_10((uint32_t)dq, (uint32_t)(dq >> 32), chain_gid, 1u, p.seed_lo, p.seed_hi);
+                w = geom_wait_of(g.x0, g.x1, p.log1mp[q_nb[lane]]);
+            }
             acc_wait += w * (int64_t)q_run[lane];
         }
         tally_flush();
@@ -341,15 +390,22 @@ __device__ __forceinline__ void flip2_body(const KParams &p, PhiloxKeys keys, co
         // re-chosen every 2^FC_PRIO_EVERY_LOG2 batches (it moves slowly; scheduling only)
         const bool every = ((prio += 4) & (((1 << FC_PRIO_EVERY_LOG2) - 1) << 2)) == 0;
         if (every) cnt_fold();
-        if (every && p.prio_nb[0] > 0) {
-            const int done = (int)p.n_steps - rem;
+        // (pp: the parameters.  The lean instances read these words again from the kernel-argument
+        // segment when the block runs instead of holding them across the loop, kparams_again)
+        auto pp = [&]() {
+            if constexpr (kTwoBody) return kparams_again();
+            else return &p;
+        };
+        if (every && pp()->prio_nb[0] > 0) {
+            const auto q = pp();
+            const int done = (int)q->n_steps - rem;
             const float eta = __uint_as_float((uint32_t)misc[1]);
             int lv;
-            if (eta > 0.0f && done * 16 >= (int)p.n_steps) {
-                const float pr = (float)(__builtin_amdgcn_s_memrealtime() - misc[0]) * (float)p.n_steps / ((float)done * eta);
-                lv = (pr > p.prio_th[0]) + (pr > p.prio_th[1]) + (pr > p.prio_th[2]);
+            if (eta > 0.0f && done * 16 >= (int)q->n_steps) {
+                const float pr = (float)(__builtin_amdgcn_s_memrealtime() - misc[0]) * (float)q->n_steps / ((float)done * eta);
+                lv = (pr > q->prio_th[0]) + (pr > q->prio_th[1]) + (pr > q->prio_th[2]);
             } else {
-                lv = (nb < p.prio_nb[0]) + (nb < p.prio_nb[1]) + (nb < p.prio_nb[2]);
+                lv = (nb < q->prio_nb[0]) + (nb < q->prio_nb[1]) + (nb < q->prio_nb[2]);
             }
             if (lv != (prio & 3)) {
                 prio = (prio & ~3) | lv;
@@ -760,8 +816,8 @@ __device__ __forceinline__ void flip2_body(const KParams &p, PhiloxKeys keys, co
                            SLIN = vote((st & LF_SLIN) != 0u), SCYC = vote((st & LF_SCYC) != 0u),
                            GAM = vote((st & LF_GAM) != 0u);
             const uint64_t EXACT = SEARCH ? vote((st & LF_EXACT) != 0u) : ~0ull;
-            const uint64_t HAS = bits_below(ns);  // (LF_HAS is lane < ns)
-            const uint64_t PROP = HIT & lane_range(pos, end);
+            const uint64_t HAS = m_below_ge1<kTwoBody>(ns);  // (LF_HAS is lane < ns; ns >= end >= 1 here)
+            const uint64_t PROP = HIT & m_range_lo_ge1<kTwoBody>(pos, end);  // (pos < end <= 64)
             // contiguity verdict when the other district does (OKT) / does not (OKN) touch
             // the outer face -- the outer-face counts are chain-global
             // BFS verdict if any; no old-district neighbour: invalid; else the run rule, exact
@@ -851,14 +907,18 @@ __device__ __forceinline__ void flip2_body(const KParams &p, PhiloxKeys keys, co
                 if (MM) sg = min(sg, __builtin_ctzll(MM) + 1);
                 const int u = UU ? __builtin_ctzll(UU) : kWave;
                 if (u < sg) sg = u;
-                uint64_t VAL = VALID1 & lane_range(pos, sg);
+                // (the _ge1 forms need sg >= 1.  sg is end, a bit's lane + 1, or u, and u = ctz(UU) can be 0 at
+                // pos = 0; the lean instances have no undecided slot -- !SEARCH: KNOWN is all ones, UU is 0, u is
+                // kWave -- and the others take lane_range, which has no such bound)
+                static_assert(!kTwoBody || !SEARCH, "m_*_ge1(.., sg): sg >= 1 holds without undecided slots only");
+                uint64_t VAL = VALID1 & m_range_lo_ge1<kTwoBody>(pos, sg);
                 bool last_step = false;
                 if (__popcll(VAL) >= rem) {  // the launch's last step lies in this segment
                     sg = kth_set_bit(VAL, rem) + 1;
-                    VAL &= bits_below(sg);
+                    VAL &= m_below_ge1<kTwoBody>(sg);
                     last_step = true;
                 }
-                const uint64_t K = CAND1 & lane_range(pos, sg);
+                const uint64_t K = CAND1 & m_range_lo_ge1<kTwoBody>(pos, sg);
                 int x = kWave;  // first lane that must not be committed
                 bool stale_seg = false;
                 // The pass's marks, foreign counts and clears concern a slot's neighbours only.  LIST:
@@ -947,7 +1007,7 @@ __device__ __forceinline__ void flip2_body(const KParams &p, PhiloxKeys keys, co
                     uint64_t CONF = vote(ms < lane) | (K & vote((nbr_bits() & ltm) != 0u));
 #pragma unroll
                     for (int i = 0; i < RMAX; ++i) CONF |= vote((int)smark[cell[i]] < lane);
-                    const uint64_t XX = CONF & HAS & lane_range(pos + 1, end);
+                    const uint64_t XX = CONF & HAS & m_after_ge1<kTwoBody>(pos, end);
                     if (XX) {
                         x = __builtin_ctzll(XX);
                         stale_seg = true;
@@ -1001,10 +1061,10 @@ __device__ __forceinline__ void flip2_body(const KParams &p, PhiloxKeys keys, co
                     }
                 }
                 if (x < sg) last_step = false;
-                if (lanes(PROP & bits_below(ce)))
+                if (lanes(PROP & m_below<kTwoBody>(ce)))
                     st |= lanes(VALID1) ? (lanes(CAND1) ? (ST_VS | ST_AC) : ST_VS) : (lanes(OK1) ? ST_IP : ST_IC);
-                rem -= __popcll(VAL & bits_below(ce));
-                const uint64_t AP = K & bits_below(ce);
+                rem -= __popcll(VAL & m_below<kTwoBody>(ce));
+                const uint64_t AP = K & m_below<kTwoBody>(ce);
                 if (AP) {
                     FC_PROF(7, __popcll(AP));
                     const bool me = lanes(AP);
@@ -1097,18 +1157,18 @@ __device__ __forceinline__ void flip2_body(const KParams &p, PhiloxKeys keys, co
             const uint64_t VAL = VALID;
             const uint64_t EV = C0 | (PROP & ~KNOWN);
             const int f = EV ? __builtin_ctzll(EV) : end;
-            const uint64_t segv = VAL & bits_below(f);
+            const uint64_t segv = VAL & m_below<kTwoBody>(f);
             const int nvalid = __popcll(segv);
             const uint32_t bits = lanes(VALID) ? ST_VS : (lanes(INV_CONTIG) ? ST_IC : ST_IP);
             if (nvalid >= rem) {  // the launch's last step lies before f
                 const int e = kth_set_bit(segv, rem);
-                st |= lanes(PROP & bits_below(e + 1)) ? bits : 0u;
+                st |= lanes(PROP & m_upto<kTwoBody>(e)) ? bits : 0u;  // (e < 64)
                 rem = 0;
                 end = e + 1;
                 target_hit = true;
                 break;
             }
-            st |= lanes(PROP & bits_below(f)) ? bits : 0u;
+            st |= lanes(PROP & m_below<kTwoBody>(f)) ? bits : 0u;
             rem -= nvalid;
             pos = f;
             if (f >= end) {
@@ -1160,7 +1220,7 @@ __device__ __forceinline__ void flip2_body(const KParams &p, PhiloxKeys keys, co
             uint32_t eqm = 0;
 #pragma unroll
             for (int i = 0; i < RMAX; ++i) eqm |= (uint32_t)(cell[i] == vf) << i;
-            const uint64_t aff = (vote(v == vf) | vote(eqm != 0u)) & HAS & lane_range(f + 1, end);
+            const uint64_t aff = (vote(v == vf) | vote(eqm != 0u)) & HAS & m_after_ge1<kTwoBody>(f, end);  // (f < end)
             if (aff) FC_PROF(13, 1);
             const uint64_t ent = ENTER;
             const int dnb = __popcll(ent) - __popcll(LEAVE);
@@ -1243,7 +1303,7 @@ __device__ __forceinline__ void flip2_body(const KParams &p, PhiloxKeys keys, co
         const int next_acc = later_acc ? __builtin_ctzll(later_acc) : end;
         const int run_len = is_acc ? 1 + __popcll(VSM & lane_range(ln + 1, next_acc)) : 0;
         const int first_acc = ACCM ? __builtin_ctzll(ACCM) : end;
-        const int r0 = __popcll(VSM & bits_below(first_acc));
+        const int r0 = __popcll(VSM & m_below<kTwoBody>(first_acc));
         int64_t my_wait = 0;
         if (XTRA && want_wait && !defer && is_acc) {
             Words4 g;

@@ -14,6 +14,8 @@ Usage: python3 tools/loop_mix.py LISTING.s 'flip2_kernel<8, 4, false, false, fal
            [--marker REGEX]   the instruction that separates regions (default: the stamps' clock read)
            [--by-line]        per source line, largest first (needs a listing with line tables)
            [--top N]          rows of the per-line table (default 40; 0: all)
+           [--sort KEY]       rank the per-line table by "issue" (VALU + SALU + LDS, the default) or by
+                              "scalar" (SALU + s_waitcnt + s_nop + branches: what the vector count leaves out)
 
 --by-line attributes every instruction of each large outermost loop (a kernel that carries its body
 twice, as the lean flip2_kernel instances do, has two batch loops: both are listed) to the source
@@ -22,7 +24,15 @@ line: every vote shows under the one line of its helper.  The column pairs count
 of a lane mask through a 0 / 1 register: a v_cmp_ne_u32 mask', 0, v whose v was last written, in
 the same block, by v_cndmask_b32 v, 0, 1, mask.  The two instructions give back the mask they
 started from; they are what a vote over a bool composed per lane costs beyond its compares
-(fc_device.h, vote), and each pair is charged to the line of its compare.  The listing it needs:
+(fc_device.h, vote), and each pair is charged to the line of its compare.  The columns wait, nop
+and branch count s_waitcnt, s_nop and the branch instructions.  The column spill counts the
+v_readlane_b32 / v_writelane_b32 that move a scalar register out of or into the kernel's SGPR-spill
+registers: the vector registers that, in the whole kernel, only v_writelane_b32 writes (a reload is
+a vector issue slot of the loop that does no chain work; they are VALU and are counted there too).
+The detection is a heuristic: a destination is the first operand of the v_*, ds_read / ds_*_rtn, global,
+buffer, flat and scratch load families only, so a register that some other writer (v_swap_b32's second
+operand, ds_consume / ds_append, image or tbuffer loads) shares with v_writelane_b32 would be misreported.
+The listing it needs:
 
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -gline-tables-only --cuda-device-only -S \
         -o flip2.s flipcomplexityempirical_amd/csrc/fc_flip2.hip
@@ -140,27 +150,55 @@ def file_table(lines):
 SEL01 = re.compile(r"^v_cndmask_b32\w*\s+(v\d+), 0, 1, (?:s\[|vcc)")
 CMP0 = re.compile(r"^v_cmp_ne_u32\w*\s+(?:s\[\d+:\d+\]|vcc), 0, (v\d+)$")
 DEST = re.compile(r"^v_\w+\s+(v\d+)\b")
+# an instruction's first operand where it is a vector destination (single register or range)
+VDEST = re.compile(r"^(?:v_|ds_read|ds_bpermute|ds_permute|ds_\w+_rtn|global_load|global_atomic\w+_rtn|buffer_load|flat_load|"
+                   r"scratch_load)\w*\s+v(?:(\d+)|\[(\d+):(\d+)\])")
+LANE_MOVE = re.compile(r"^v_(readlane|writelane)_b32\s+(\w+), (\w+),")
 
 
-def by_line(inl, files, top):
-    """Per-line VALU / SALU / LDS table of the blocks inl, and the mask round trips (pairs)."""
-    cols = ("VALU", "SALU", "LDS", "pairs", "all")
+def spill_registers(blocks):
+    """The kernel's SGPR-spill VGPRs: written by v_writelane_b32 and by nothing else."""
+    lane_written, written = set(), set()
+    for b in blocks:
+        for text, _ in b["full"]:
+            m = VDEST.match(text)
+            if not m:
+                continue
+            regs = {int(m.group(1))} if m.group(1) else set(range(int(m.group(2)), int(m.group(3)) + 1))
+            (lane_written if text.startswith("v_writelane_b32") else written).update(regs)
+    return {f"v{r}" for r in lane_written - written}
+
+
+def is_spill_move(text, spill):
+    m = LANE_MOVE.match(text)
+    return bool(m) and (m.group(2) if m.group(1) == "writelane" else m.group(3)) in spill
+
+
+SORT_KEYS = {"issue": ("VALU", "SALU", "LDS"), "scalar": ("SALU", "wait", "nop", "branch")}
+
+
+def by_line(inl, files, top, spill=frozenset(), sort="issue"):
+    """Per-line table of the blocks inl by instruction class, the SGPR-spill lane moves (spill) and
+    the mask round trips (pairs)."""
+    cols = ("VALU", "SALU", "LDS", "wait", "nop", "branch", "spill", "pairs", "all")
     tab = {}
     for b in inl:
         sel01 = set()  # registers holding a mask as 0 / 1
         for text, loc in b["full"]:
             t = tab.setdefault(loc, dict.fromkeys(cols, 0))
-            cls = classify(text.split()[0])
+            mn = text.split()[0]
+            cls = "wait" if mn.startswith("s_waitcnt") else "nop" if mn.startswith("s_nop") else classify(mn)
             if cls in t:
                 t[cls] += 1
             t["all"] += 1
+            t["spill"] += is_spill_move(text, spill)
             if (m := CMP0.match(text)) and m.group(1) in sel01:
                 t["pairs"] += 1
             if m := DEST.match(text):
                 sel01.discard(m.group(1))
             if m := SEL01.match(text):
                 sel01.add(m.group(1))
-    rows = sorted(tab.items(), key=lambda kv: (-kv[1]["VALU"] - kv[1]["SALU"] - kv[1]["LDS"], str(kv[0])))
+    rows = sorted(tab.items(), key=lambda kv: (-sum(kv[1][c] for c in SORT_KEYS[sort]), str(kv[0])))
     fmt = lambda name, t: f"{name:<44}" + "".join(f"{t[c]:>7}" for c in cols)
     print(f"{'file:line':<44}" + "".join(f"{c:>7}" for c in cols))
     for loc, t in rows[:top or None]:
@@ -183,6 +221,7 @@ def main():
     ap.add_argument("--marker", default=r"^s_memtime")
     ap.add_argument("--by-line", action="store_true")
     ap.add_argument("--top", type=int, default=40)
+    ap.add_argument("--sort", choices=sorted(SORT_KEYS), default="issue")
     args = ap.parse_args()
     with open(args.listing) as fh:
         lines = fh.read().splitlines()
@@ -206,13 +245,15 @@ def main():
         if not any(loc for b in blocks for _, loc in b["full"]):
             sys.exit("no .loc directives: compile the listing with -gline-tables-only")
         files = file_table(lines)
+        spill = spill_registers(blocks)
+        print(f"SGPR-spill registers (written by v_writelane_b32 only): {' '.join(sorted(spill)) or 'none'}")
         # the batch loops: every outermost loop at least half the largest one's size
         for h in [h for h in top if 2 * top[h] >= max(top.values())]:
             inl = [b for b in blocks if b["loops"] and b["loops"][0] == h]
             print(f"\nloop {h}: {len(inl)} blocks, static instructions by source line")
             print(f"{'':<28}" + "".join(f"{c:>9}" for c in CLASSES) + f"{'total':>9}")
             print(row("whole loop", mix([m for b in inl for m in b["insts"]])))
-            by_line(inl, files, args.top)
+            by_line(inl, files, args.top, spill, args.sort)
         return
     main_loop = max(top, key=top.get)
     inl = [b for b in blocks if b["loops"] and b["loops"][0] == main_loop]
